@@ -654,7 +654,8 @@ class PlanRunner:
             torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(steps):
-            self.train_step()
+            # kept for callers that report what the timed path computed
+            self.last_loss = self.train_step()
         if dist.is_initialized():
             dist.barrier()
         if torch.cuda.is_available():

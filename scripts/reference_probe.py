@@ -14,9 +14,12 @@ Modes:
 """
 
 import json
+import os
 import sys
 
-REFERENCE = "/root/reference"
+# the reference checkout to probe; the parity tests pass it on from their
+# own environment
+REFERENCE = os.environ["METIS_REFERENCE_DIR"]
 sys.path.insert(0, REFERENCE)
 
 
