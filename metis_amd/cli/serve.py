@@ -11,11 +11,12 @@ random-init model for smoke testing:
   -> {"tokens": [[prompt + continuation]]}
 
 Scope: single process (tp=pp=1), token-id interface (tokenizers are
-deployment-specific). The single-query decode kernel is the default
-GPU decode path (round 2); ``--continuous`` serves every request
-through one shared ContinuousBatcher decode loop (requests join and
-leave the running batch between steps) instead of per-request
-generate() calls.
+deployment-specific). The single-query decode kernel (decode.hip) is
+the default GPU decode path of per-request generate() calls;
+``--continuous`` serves every request through one shared
+ContinuousBatcher decode loop (requests join and leave the running
+batch between steps), whose padded ragged cache is read by the split-S
+ragged kernel (decode_ragged.hip) instead.
 """
 
 from __future__ import annotations

@@ -361,9 +361,13 @@ class GPTBlock(nn.Module):
             q, k, v = qkv_split_transpose(
                 qkv, self.heads_per_rank, self.heads_per_rank, self.head_dim)
             k, v = cache.append(layer_idx, k, v)
-            am = getattr(cache, "attention_mask", None)
-            mask = am(k.size(2), q.device) if am is not None else None
-            attn = self._cached_attention(q, k, v, mask)
+            if hasattr(cache, "kv_lens") and q.size(2) == 1:
+                # ragged cache: per-row lengths, padded views as they are
+                attn = decode_attention(q, k, v, kv_lens=cache.kv_lens())
+            else:
+                am = getattr(cache, "attention_mask", None)
+                mask = am(k.size(2), q.device) if am is not None else None
+                attn = self._cached_attention(q, k, v, mask)
             x = residual + self.proj(heads_merge(attn), tp_group)
             residual = x
             y = self.fc1(self.ln_mlp(x), tp_group)

@@ -114,10 +114,16 @@ class LlamaBlock(nn.Module):
                 q = apply_rope(q, self.rope_base, pos_offset=pos_offset)
                 k = apply_rope(k, self.rope_base, pos_offset=pos_offset)
             k, v = cache.append(layer_idx, k, v)
-            am = getattr(cache, "attention_mask", None)
-            rag_mask = am(k.size(2), q.device) if am is not None else None
             new, total = q.size(2), k.size(2)
-            if rag_mask is not None:
+            ragged = hasattr(cache, "kv_lens") and new == 1
+            am = getattr(cache, "attention_mask", None)
+            rag_mask = (am(total, q.device)
+                        if am is not None and not ragged else None)
+            if ragged:
+                # ragged cache: per-row lengths, padded views as they
+                # are, GQA mapped inside (no repeat_interleave copies)
+                attn = decode_attention(q, k, v, kv_lens=cache.kv_lens())
+            elif rag_mask is not None:
                 rep = hq // hkv
                 attn = F.scaled_dot_product_attention(
                     q, k.repeat_interleave(rep, dim=1),

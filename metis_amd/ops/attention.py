@@ -77,21 +77,63 @@ def flash_attention(
     )
 
 
-def decode_attention(q: torch.Tensor, k: torch.Tensor,
-                     v: torch.Tensor) -> torch.Tensor:
+def _ragged_supported(q: torch.Tensor, k: torch.Tensor) -> bool:
+    """Shapes decode_ragged.hip is instantiated for."""
+    h, hkv = q.size(1), k.size(1)
+    return (q.is_cuda and q.dtype == torch.bfloat16
+            and k.dtype == torch.bfloat16 and q.size(2) == 1
+            and q.size(-1) in (64, 80, 96, 128)
+            and hkv > 0 and h % hkv == 0 and h // hkv in (1, 2, 4, 8))
+
+
+def decode_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+                     kv_lens: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Single-query attention over cached K/V (serving decode step):
     q [B, H, 1, D] vs k/v [B, Hkv, S, D], GQA mapped in-kernel. The
     gfx950 kernel (decode.hip) is the DEFAULT on supported shapes —
     GPU-validated round 2 (numerics test + measured llama3-1b decode
     317 -> 295 ms for 8x64 tokens, +7.4% tok/s, gpurun_out/r2ab);
-    METIS_DECODE_KERNEL=0 forces the SDPA fallback."""
+    METIS_DECODE_KERNEL=0 forces the SDPA fallback.
+
+    ``kv_lens`` [B] (ragged / continuous batching): row b attends only
+    positions < kv_lens[b] of the padded cache. Supported shapes run the
+    split-S kernel (decode_ragged.hip), which reads strided cache views
+    in place and never loads the padding; anything else builds the
+    length mask and calls SDPA (which needs kv_lens >= 1: a fully masked
+    row is NaN there, where the kernel writes zeros). METIS_DECODE_SPLIT=1 routes the dense
+    case through the split-S kernel too (A/B timing; off by default)."""
     import os
 
+    kernel_on = os.environ.get("METIS_DECODE_KERNEL", "1") == "1"
+    scale = 1.0 / math.sqrt(q.size(-1))
+    if kv_lens is not None:
+        if kernel_on and _ragged_supported(q, k):
+            ext = _ops.require_extension()
+            lens = kv_lens.to(device=q.device, dtype=torch.int32)
+            return ext.attn_decode_ragged(q, k, v, lens, scale)
+        # same computation the models' mask-SDPA branch did; padded
+        # positions are zeroed so stale NaN/inf there cannot leak
+        # through 0 * NaN (exact no-op on finite padding)
+        cols = torch.arange(k.size(2), device=q.device)
+        keep = cols[None] < kv_lens.to(q.device)[:, None]       # [B, S]
+        k = torch.where(keep[:, None, :, None], k, 0)
+        v = torch.where(keep[:, None, :, None], v, 0)
+        if k.size(1) != q.size(1):
+            rep = q.size(1) // k.size(1)
+            k = k.repeat_interleave(rep, dim=1)
+            v = v.repeat_interleave(rep, dim=1)
+        return F.scaled_dot_product_attention(
+            q, k, v, attn_mask=keep[:, None, None])
+
     if (q.is_cuda and q.dtype == torch.bfloat16 and q.size(2) == 1
-            and q.size(-1) in (64, 80, 96, 128)
-            and os.environ.get("METIS_DECODE_KERNEL", "1") == "1"):
+            and q.size(-1) in (64, 80, 96, 128) and kernel_on):
         ext = _ops.require_extension()
-        return ext.attn_decode(q, k, v, 1.0 / math.sqrt(q.size(-1)))
+        if (os.environ.get("METIS_DECODE_SPLIT") == "1"
+                and _ragged_supported(q, k)):
+            lens = torch.full((q.size(0),), k.size(2), dtype=torch.int32,
+                              device=q.device)
+            return ext.attn_decode_ragged(q, k, v, lens, scale)
+        return ext.attn_decode(q, k, v, scale)
     if k.size(1) != q.size(1):
         rep = q.size(1) // k.size(1)
         k = k.repeat_interleave(rep, dim=1)

@@ -15,6 +15,9 @@ void adamw_step(
     double weight_decay, long step, double grad_scale);
 torch::Tensor attn_decode(
     torch::Tensor q, torch::Tensor k, torch::Tensor v, double scale);
+torch::Tensor attn_decode_ragged(
+    torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor kv_lens,
+    double scale, long num_splits);
 torch::Tensor ce_row_max(torch::Tensor logits);
 torch::Tensor ce_row_sumexp(torch::Tensor logits, torch::Tensor m);
 std::vector<torch::Tensor> qkv_rope_split(
@@ -97,6 +100,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("heads_unmerge", &heads_unmerge, "[B,S,H*D] -> [B,H,S,D]");
     m.def("attn_decode", &attn_decode,
           "single-query attention over cached K/V (GQA, online softmax)");
+    m.def("attn_decode_ragged", &attn_decode_ragged,
+          "ragged split-S single-query attention over a padded K/V cache "
+          "(per-row kv_lens, strided views, GQA group per workgroup)",
+          pybind11::arg("q"), pybind11::arg("k"), pybind11::arg("v"),
+          pybind11::arg("kv_lens"), pybind11::arg("scale"),
+          pybind11::arg("num_splits") = 0);
     m.def("ce_row_max", &ce_row_max, "per-row max of bf16 logits (fp32)");
     m.def("ce_row_sumexp", &ce_row_sumexp,
           "per-row sum(exp(x - m)) of bf16 logits (fp32)");

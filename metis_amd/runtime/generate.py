@@ -3,9 +3,12 @@
 The reference is a training planner with no inference at all; this adds
 the decode loop the models need to serve: per-block KV caches, one
 prefill pass, then one-token incremental forwards. CPU tests prove
-incremental logits match a full forward position-for-position; the
-decode-optimized attention kernel (single-query flash) is a round-2 GPU
-item — this path uses SDPA over the cache.
+incremental logits match a full forward position-for-position. On the
+GPU a one-token step runs a hand-written single-query kernel through
+``decode_attention``: decode.hip for the dense ``KVCache``, and the
+split-S ragged kernel (decode_ragged.hip) for ``RaggedKVCache``, which
+reads the padded buffers in place with per-row lengths. Prefill chunks
+and unsupported shapes use SDPA over the cache.
 """
 
 from __future__ import annotations
@@ -79,6 +82,12 @@ class RaggedKVCache:
         (its prefix plus the token just appended)."""
         cols = torch.arange(total, device=device)
         return (cols[None] <= self.lengths.to(device)[:, None])[:, None, None]
+
+    def kv_lens(self) -> torch.Tensor:
+        """[b] valid K/V positions per row for the current step: the
+        prefix plus the token just appended (what attention_mask()
+        expresses as a mask), on the cache's device."""
+        return self.lengths + 1
 
     def advance(self) -> None:
         self.lengths += 1
@@ -191,8 +200,11 @@ class ContinuousBatcher:
     token budget or ``eos_id``. Retired slots are reused immediately —
     a long request no longer blocks short ones behind it.
 
-    Single process (tp=pp=1), device-agnostic (CPU tests; the GPU path
-    uses the default-on single-query decode kernel via the models).
+    Single process (tp=pp=1), device-agnostic. On the GPU every decode
+    step runs the ragged split-S kernel (decode_ragged.hip) via the
+    models: it takes ``cache.kv_lens()`` and the ``[:, :, :upto]``
+    buffer views as they are. METIS_DECODE_KERNEL=0, CPU and
+    unsupported shapes take the length-mask SDPA path instead.
     """
 
     def __init__(self, model, capacity: int, max_batch: int = 8,
