@@ -94,7 +94,8 @@ class FusedAdamW:
             if g is None:
                 self._grad_flat[off:off + n].zero_()
             else:
-                self._grad_flat[off:off + n].copy_(g.reshape(-1).float())
+                # one converting copy (bf16 -> fp32 is exact), no fp32 temp
+                self._grad_flat[off:off + n].copy_(g.reshape(-1))
         return self._grad_flat
 
     @property

@@ -46,9 +46,11 @@ class _FlashAttention(torch.autograd.Function):
     def backward(ctx, d_o):
         ext = _ops.require_extension()
         q, k, v, o, lse = ctx.saved_tensors
-        delta = (d_o.float() * o.float()).sum(-1)   # [B, H, S]
-        dq, dk_h, dv_h = ext.attn_bwd(q, k, v, d_o.contiguous(), lse,
-                                      delta.contiguous(), ctx.scale)
+        # an expanded (zero-stride) gradient, e.g. from o.sum().backward(),
+        # is materialised once here and shared by both kernels
+        d_o = d_o.contiguous()
+        delta = ext.attn_bwd_delta(o, d_o)          # fp32 [B, H, S]
+        dq, dk_h, dv_h = ext.attn_bwd(q, k, v, d_o, lse, delta, ctx.scale)
         h, hkv = q.size(1), k.size(1)
         if h != hkv:
             b, _, s, d = q.shape

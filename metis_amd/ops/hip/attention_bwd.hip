@@ -449,7 +449,74 @@ void attn_bwd_dkv_kernel(
     }
 }
 
+// delta[row] = sum_d dO[row, d] * O[row, d] in fp32: the softmax-backward
+// row term both kernels above consume. 16 lanes per row, one bf16x8 chunk
+// each (D/8 = 8/10/12/16 of them live), 4 rows per wave step, DELTA_U steps
+// in flight per thread; o and dO are read once, 4 B per row written.
+constexpr int DELTA_THREADS = 256;
+constexpr int DELTA_U = 4;
+
+__global__ void __launch_bounds__(DELTA_THREADS) attn_bwd_delta_kernel(
+    const bf16x8* __restrict__ o,
+    const bf16x8* __restrict__ d_o,
+    float* __restrict__ delta,
+    long rows,
+    int dv) {                       // D / 8 chunks per row, <= 16
+    const int sub = threadIdx.x & 15;
+    const bool live = sub < dv;
+    const int ci = live ? sub : dv - 1;     // idle lanes re-read a valid chunk
+    const long rows_per_block = DELTA_THREADS / 16 * DELTA_U;
+    const long row0 = (long)blockIdx.x * rows_per_block + threadIdx.x / 16;
+
+    bf16x8 a[DELTA_U], b[DELTA_U];
+    #pragma unroll
+    for (int u = 0; u < DELTA_U; ++u) {
+        long row = row0 + u * (DELTA_THREADS / 16);
+        if (row >= rows) row = rows - 1;    // clamped, not stored below
+        a[u] = o[row * dv + ci];
+        b[u] = d_o[row * dv + ci];
+    }
+    #pragma unroll
+    for (int u = 0; u < DELTA_U; ++u) {
+        float s = 0.f;
+        #pragma unroll
+        for (int k = 0; k < 8; ++k)
+            s += bf16_bits_to_float(a[u][k]) * bf16_bits_to_float(b[u][k]);
+        if (!live) s = 0.f;
+        #pragma unroll
+        for (int off = 8; off > 0; off >>= 1) s += __shfl_xor(s, off, WAVE_SIZE);
+        const long row = row0 + u * (DELTA_THREADS / 16);
+        if (sub == 0 && row < rows) delta[row] = s;
+    }
+}
+
 }  // namespace
+
+torch::Tensor attn_bwd_delta(torch::Tensor o, torch::Tensor d_o) {
+    TORCH_CHECK(o.is_cuda() && o.dtype() == torch::kBFloat16
+                && d_o.is_cuda() && d_o.dtype() == torch::kBFloat16,
+                "o and d_o must be CUDA bf16");
+    TORCH_CHECK(o.dim() == 4 && o.sizes() == d_o.sizes(),
+                "o and d_o must both be [B, H, S, D]");
+    TORCH_CHECK(o.is_contiguous() && d_o.is_contiguous(),
+                "o and d_o must be contiguous");
+    const long D = o.size(3);
+    TORCH_CHECK(D == 64 || D == 80 || D == 96 || D == 128,
+                "head dim must be 64/80/96/128, got ", D);
+    const long rows = o.numel() / D;
+    auto delta = torch::empty({o.size(0), o.size(1), o.size(2)},
+                              o.options().dtype(torch::kFloat32));
+    if (rows == 0) return delta;
+    const long rows_per_block = DELTA_THREADS / 16 * DELTA_U;
+    const long grid = (rows + rows_per_block - 1) / rows_per_block;
+    hipLaunchKernelGGL(attn_bwd_delta_kernel, dim3((unsigned)grid),
+        dim3(DELTA_THREADS), 0, c10::hip::getCurrentHIPStream().stream(),
+        reinterpret_cast<const bf16x8*>(o.data_ptr()),
+        reinterpret_cast<const bf16x8*>(d_o.data_ptr()),
+        delta.data_ptr<float>(), rows, (int)(D / 8));
+    HIP_CHECK_LAST();
+    return delta;
+}
 
 std::vector<torch::Tensor> attn_bwd(
     torch::Tensor q, torch::Tensor k, torch::Tensor v,

@@ -39,6 +39,7 @@ std::vector<torch::Tensor> attn_bwd(
     torch::Tensor q, torch::Tensor k, torch::Tensor v,
     torch::Tensor d_o, torch::Tensor lse, torch::Tensor delta,
     double scale);
+torch::Tensor attn_bwd_delta(torch::Tensor o, torch::Tensor d_o);
 torch::Tensor gemm_bf16(
     torch::Tensor a, torch::Tensor b_nk, c10::optional<torch::Tensor> bias,
     long epilogue);
@@ -76,6 +77,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "flash attention forward (causal, GQA) -> (O, LSE)");
     m.def("attn_bwd", &attn_bwd,
           "flash attention backward -> (dQ, dK_per_head, dV_per_head)");
+    m.def("attn_bwd_delta", &attn_bwd_delta,
+          "rowsum(dO * O) in fp32 -> [B,H,S] (contiguous bf16 inputs)");
     m.def("gemm_bf16", &gemm_bf16,
           "MFMA bf16 GEMM A[M,K] @ B[N,K]^T with fused epilogue "
           "(0=none, 1=bias, 2=bias+gelu)");

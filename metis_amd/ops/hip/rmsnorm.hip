@@ -1,11 +1,13 @@
 // Fused RMSNorm forward/backward for gfx950 (bf16 I/O, fp32 statistics).
 // Llama-family norm: y = x * rstd * gamma, rstd = 1/sqrt(mean(x^2) + eps).
-// Memory-bound; same vectorized structure as layernorm.hip.
+// Memory-bound; same vectorized structure as layernorm.hip. The backward
+// for H <= 8192 is the streaming kernel of norm_bwd.h.
 
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
 
 #include "common.h"
+#include "norm_bwd.h"
 
 namespace {
 
@@ -107,17 +109,6 @@ __global__ void rms_bwd_kernel(
         dgamma_part[(long)blockIdx.x * H + i] = dg[(i % VEC) * hv + i / VEC];
 }
 
-__global__ void rms_bwd_reduce_kernel(
-    const float* __restrict__ dgamma_part,
-    float* __restrict__ dgamma,
-    int nslabs, int H) {
-    const int col = blockIdx.x * blockDim.x + threadIdx.x;
-    if (col >= H) return;
-    float g = 0.f;
-    for (int s = 0; s < nslabs; ++s) g += dgamma_part[(long)s * H + col];
-    dgamma[col] = g;
-}
-
 }  // namespace
 
 std::vector<torch::Tensor> rmsnorm_fwd(
@@ -145,32 +136,49 @@ std::vector<torch::Tensor> rmsnorm_fwd(
 
 std::vector<torch::Tensor> rmsnorm_bwd(
     torch::Tensor dy, torch::Tensor x, torch::Tensor gamma, torch::Tensor rstd) {
+    TORCH_CHECK(dy.is_cuda() && dy.dtype() == torch::kBFloat16, "dy must be CUDA bf16");
+    TORCH_CHECK(x.is_contiguous() && rstd.is_contiguous(),
+                "x and rstd must be contiguous");
     auto dyc = dy.contiguous();
     const long H = x.size(-1);
     const long rows = x.numel() / H;
+    TORCH_CHECK(H % 8 == 0 && H <= 16384,
+                "rmsnorm bwd supports hidden size % 8 == 0, <= 16384");
+    TORCH_CHECK(rows >= 1 && dyc.numel() == x.numel() && rstd.numel() == rows,
+                "rmsnorm bwd: shape mismatch");
 
     auto dx = torch::empty_like(x);
-    const int grid = (int)std::min<long>(rows, 128);
-    auto dgamma_part = torch::empty({grid, H}, x.options().dtype(torch::kFloat32));
+    auto f32 = x.options().dtype(torch::kFloat32);
     auto gamma_f = gamma.to(torch::kFloat32).contiguous();
+    auto stream = c10::hip::getCurrentHIPStream().stream();
 
-    TORCH_CHECK(H <= 16384, "rmsnorm bwd supports hidden size <= 16384");
-    hipLaunchKernelGGL(rms_bwd_kernel, dim3(grid), dim3(BLOCK), H * (int)sizeof(float),
-        c10::hip::getCurrentHIPStream().stream(),
-        reinterpret_cast<const bf16x8*>(dyc.data_ptr()),
-        reinterpret_cast<const bf16x8*>(x.data_ptr()),
-        reinterpret_cast<const floatx4*>(gamma_f.data_ptr()),
-        rstd.data_ptr<float>(),
-        reinterpret_cast<bf16x8*>(dx.data_ptr()),
-        dgamma_part.data_ptr<float>(), (int)rows, (int)(H / 8));
+    // H <= 8192: streaming kernel (norm_bwd.h); wider rows do not fit one
+    // chunk per thread and keep the row-at-a-time kernel above
+    const bool streaming = H <= 8192;
+    const int grid = streaming ? norm_bwd::grid_for<true>(rows, H)
+                               : (int)std::min<long>(rows, 128);
+    auto dgamma_part = torch::empty({grid, H}, f32);
+    if (streaming) {
+        norm_bwd::launch_main<true>(
+            dyc.data_ptr(), x.data_ptr(), gamma_f.data_ptr<float>(), nullptr,
+            rstd.data_ptr<float>(), dx.data_ptr(),
+            dgamma_part.data_ptr<float>(), nullptr, rows, H, grid, stream);
+    } else {
+        hipLaunchKernelGGL(rms_bwd_kernel, dim3(grid), dim3(BLOCK),
+            H * (int)sizeof(float), stream,
+            reinterpret_cast<const bf16x8*>(dyc.data_ptr()),
+            reinterpret_cast<const bf16x8*>(x.data_ptr()),
+            reinterpret_cast<const floatx4*>(gamma_f.data_ptr()),
+            rstd.data_ptr<float>(),
+            reinterpret_cast<bf16x8*>(dx.data_ptr()),
+            dgamma_part.data_ptr<float>(), (int)rows, (int)(H / 8));
+    }
     HIP_CHECK_LAST();
 
-    auto dgamma = torch::empty({H}, x.options().dtype(torch::kFloat32));
-    hipLaunchKernelGGL(rms_bwd_reduce_kernel,
-        dim3((H + 255) / 256), dim3(256), 0,
-        c10::hip::getCurrentHIPStream().stream(),
-        dgamma_part.data_ptr<float>(), dgamma.data_ptr<float>(),
-        grid, (int)H);
+    auto dgamma = torch::empty({H}, f32);
+    norm_bwd::launch_reduce<true>(
+        dgamma_part.data_ptr<float>(), nullptr, dgamma.data_ptr<float>(),
+        nullptr, grid, (int)H, stream);
     HIP_CHECK_LAST();
     return {dx, dgamma};
 }

@@ -1,0 +1,99 @@
+"""GPU tests: streaming LayerNorm / RMSNorm backward over the shape grid.
+
+Hidden sizes cover one lane (8), exactly one wave of 16-byte chunks (512),
+a partial last wave (768), the flagship (2560, 4 rows per iteration), 4096
+(2 rows per iteration) and the upper bound (8192, 16 waves). Row counts
+cover 1, fewer rows than one iteration loads (3), partial last iterations
+(33, 257) and, at H=512, more rows than grid x rows-per-iteration (5000:
+the grid-stride loop and the full slab reduce both run).
+
+Reference: fp32 torch autograd on the same bf16 inputs. The statistics fed
+to the kernels are computed in fp32 torch too, so only the backward is
+under test.
+"""
+
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+if torch.cuda.is_available():
+    from metis_amd.ops import require_extension
+else:
+    pytest.skip("requires MI355X GPU", allow_module_level=True)
+
+EPS = 1e-5
+HIDDEN = (8, 512, 768, 2560, 4096, 8192)
+ROWS = (1, 3, 33, 257)
+CASES = [(r, h) for h in HIDDEN for r in ROWS] + [(5000, 512)]
+
+
+@pytest.fixture(scope="module")
+def ext():
+    return require_extension()
+
+
+def _inputs(rows, hidden):
+    torch.manual_seed(rows * 10007 + hidden)
+    x = torch.randn(rows, hidden, device="cuda", dtype=torch.bfloat16)
+    dy = torch.randn(rows, hidden, device="cuda", dtype=torch.bfloat16)
+    gamma = torch.randn(hidden, device="cuda", dtype=torch.float32)
+    return x, dy, gamma
+
+
+def _check(name, got, want, rows, hidden):
+    """dgamma/dbeta: inputs are exact in fp32, so only the summation order
+    differs (~1e-6 relative); a dropped or doubled row moves a column by
+    percents."""
+    err = (got - want).abs().max().item()
+    bound = 1e-3 * want.abs().max().item()
+    print(f"{name} rows={rows} H={hidden}: max abs err {err:.3e}, bound {bound:.3e}")
+    assert err <= bound, (name, rows, hidden, err, bound)
+
+
+@pytest.mark.parametrize("rows,hidden", CASES)
+def test_layernorm_bwd_shapes(ext, rows, hidden):
+    x, dy, gamma = _inputs(rows, hidden)
+    xf = x.float().requires_grad_(True)
+    gf = gamma.clone().requires_grad_(True)
+    bf = torch.zeros_like(gamma).requires_grad_(True)
+    torch.nn.functional.layer_norm(xf, (hidden,), gf, bf, EPS).backward(dy.float())
+
+    mean = x.float().mean(-1)
+    rstd = torch.rsqrt(x.float().var(-1, unbiased=False) + EPS)
+    dx, dgamma, dbeta = ext.layernorm_bwd(dy, x, gamma, mean, rstd)
+    assert dx.shape == x.shape and dx.dtype == torch.bfloat16
+    assert dgamma.shape == (hidden,) and dbeta.shape == (hidden,)
+
+    dx_err = (dx.float() - xf.grad).abs().max().item()
+    print(f"ln dx rows={rows} H={hidden}: max abs err {dx_err:.3e}")
+    assert torch.allclose(dx.float(), xf.grad, atol=5e-2, rtol=5e-2)
+    _check("ln dgamma", dgamma, gf.grad, rows, hidden)
+    _check("ln dbeta", dbeta, bf.grad, rows, hidden)
+
+    again = ext.layernorm_bwd(dy, x, gamma, mean, rstd)
+    for a, b in zip((dx, dgamma, dbeta), again):
+        assert torch.equal(a, b)
+
+
+@pytest.mark.parametrize("rows,hidden", CASES)
+def test_rmsnorm_bwd_shapes(ext, rows, hidden):
+    x, dy, gamma = _inputs(rows, hidden)
+    xf = x.float().requires_grad_(True)
+    gf = gamma.clone().requires_grad_(True)
+    rstd = torch.rsqrt(x.float().pow(2).mean(-1) + EPS)
+    (xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + EPS) * gf).backward(
+        dy.float())
+
+    dx, dgamma = ext.rmsnorm_bwd(dy, x, gamma, rstd)
+    assert dx.shape == x.shape and dx.dtype == torch.bfloat16
+    assert dgamma.shape == (hidden,)
+
+    dx_err = (dx.float() - xf.grad).abs().max().item()
+    print(f"rms dx rows={rows} H={hidden}: max abs err {dx_err:.3e}")
+    assert torch.allclose(dx.float(), xf.grad, atol=5e-2, rtol=5e-2)
+    _check("rms dgamma", dgamma, gf.grad, rows, hidden)
+
+    again = ext.rmsnorm_bwd(dy, x, gamma, rstd)
+    for a, b in zip((dx, dgamma), again):
+        assert torch.equal(a, b)
