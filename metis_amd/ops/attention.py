@@ -4,10 +4,10 @@ Forward: online-softmax flash kernel (attention.hip), saving the row LSE.
 Backward: split dQ / dKV recompute kernels (attention_bwd.hip); GQA dK/dV
 come back per q-head and reduce over the group here (deterministic).
 
-Unsupported shapes (D > 128, D % 16 != 0, S % 128 != 0, non-causal) fall
-back to PyTorch SDPA (the fwd/bwd kernels tile the sequence in 128-row
-q blocks — attention.hip QBLK / attention_bwd.hip RBLK); on
-GPU-supported shapes the HIP path always runs.
+Unsupported shapes (head dim outside HEAD_DIMS, S % 128 != 0, non-causal)
+fall back to PyTorch SDPA: the kernels are template-instantiated per head
+dim and tile the sequence in 128-row q blocks (attention.hip QBLK /
+attention_bwd.hip RBLK). On GPU-supported shapes the HIP path always runs.
 """
 
 from __future__ import annotations
@@ -21,15 +21,21 @@ import torch.nn.functional as F
 from metis_amd import ops as _ops
 
 
+# head dims attention.hip, attention_bwd.hip, decode.hip and
+# decode_ragged.hip are instantiated for; anything else must not reach them
+HEAD_DIMS = (64, 80, 96, 128)
+
+
+def _head_dim_supported(d: int) -> bool:
+    return d in HEAD_DIMS
+
+
 def _supported(q: torch.Tensor) -> bool:
-    d = q.size(-1)
-    s = q.size(2)
     return (
         q.is_cuda
         and q.dtype == torch.bfloat16
-        and d % 16 == 0
-        and d <= 128
-        and s % 128 == 0
+        and _head_dim_supported(q.size(-1))
+        and q.size(2) % 128 == 0
     )
 
 
@@ -84,7 +90,7 @@ def _ragged_supported(q: torch.Tensor, k: torch.Tensor) -> bool:
     h, hkv = q.size(1), k.size(1)
     return (q.is_cuda and q.dtype == torch.bfloat16
             and k.dtype == torch.bfloat16 and q.size(2) == 1
-            and q.size(-1) in (64, 80, 96, 128)
+            and _head_dim_supported(q.size(-1))
             and hkv > 0 and h % hkv == 0 and h // hkv in (1, 2, 4, 8))
 
 
@@ -128,7 +134,7 @@ def decode_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
             q, k, v, attn_mask=keep[:, None, None])
 
     if (q.is_cuda and q.dtype == torch.bfloat16 and q.size(2) == 1
-            and q.size(-1) in (64, 80, 96, 128) and kernel_on):
+            and _head_dim_supported(q.size(-1)) and kernel_on):
         ext = _ops.require_extension()
         if (os.environ.get("METIS_DECODE_SPLIT") == "1"
                 and _ragged_supported(q, k)):

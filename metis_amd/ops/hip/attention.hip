@@ -304,10 +304,20 @@ std::vector<torch::Tensor> attn_fwd(
     TORCH_CHECK(q.is_cuda() && q.dtype() == torch::kBFloat16, "q must be CUDA bf16");
     TORCH_CHECK(q.dim() == 4, "q must be [B, H, S, D]");
     const long B = q.size(0), H = q.size(1), S = q.size(2), D = q.size(3);
+    TORCH_CHECK(k.is_cuda() && k.dtype() == torch::kBFloat16
+                && v.is_cuda() && v.dtype() == torch::kBFloat16,
+                "k and v must be CUDA bf16");
+    TORCH_CHECK(k.get_device() == q.get_device()
+                && v.get_device() == q.get_device(),
+                "q, k and v must be on the same device");
+    TORCH_CHECK(k.dim() == 4 && v.dim() == 4 && k.sizes() == v.sizes(),
+                "k and v must both be [B, Hkv, S, D]");
     const long Hkv = k.size(1);
-    TORCH_CHECK(k.size(2) == S && v.size(2) == S, "kv length mismatch");
+    TORCH_CHECK(k.size(0) == B, "k/v batch must match q");
+    TORCH_CHECK(k.size(3) == D, "k/v head dim must match q");
+    TORCH_CHECK(k.size(2) == S, "kv length mismatch");
     TORCH_CHECK(S % QBLK == 0, "sequence length must be a multiple of 128");
-    TORCH_CHECK(H % Hkv == 0, "GQA requires H % Hkv == 0");
+    TORCH_CHECK(Hkv > 0 && H % Hkv == 0, "GQA requires H % Hkv == 0");
     auto qc = q.contiguous(), kc = k.contiguous(), vc = v.contiguous();
 
     auto o = torch::empty_like(qc);

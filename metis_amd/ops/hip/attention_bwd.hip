@@ -522,9 +522,30 @@ std::vector<torch::Tensor> attn_bwd(
     torch::Tensor q, torch::Tensor k, torch::Tensor v,
     torch::Tensor d_o, torch::Tensor lse, torch::Tensor delta,
     double scale) {
-    TORCH_CHECK(q.is_cuda() && q.dtype() == torch::kBFloat16);
+    TORCH_CHECK(q.is_cuda() && q.dtype() == torch::kBFloat16, "q must be CUDA bf16");
+    TORCH_CHECK(q.dim() == 4, "q must be [B, H, S, D]");
     const long B = q.size(0), H = q.size(1), S = q.size(2), D = q.size(3);
+    TORCH_CHECK(k.is_cuda() && k.dtype() == torch::kBFloat16
+                && v.is_cuda() && v.dtype() == torch::kBFloat16
+                && d_o.is_cuda() && d_o.dtype() == torch::kBFloat16,
+                "k, v and d_o must be CUDA bf16");
+    TORCH_CHECK(lse.is_cuda() && lse.dtype() == torch::kFloat32
+                && delta.is_cuda() && delta.dtype() == torch::kFloat32,
+                "lse and delta must be CUDA fp32");
+    for (const torch::Tensor* t : {&k, &v, &d_o, &lse, &delta})
+        TORCH_CHECK(t->get_device() == q.get_device(),
+                    "all attn_bwd arguments must be on the same device");
+    TORCH_CHECK(k.dim() == 4 && v.dim() == 4 && k.sizes() == v.sizes(),
+                "k and v must both be [B, Hkv, S, D]");
     const long Hkv = k.size(1);
+    TORCH_CHECK(k.size(0) == B, "k/v batch must match q");
+    TORCH_CHECK(k.size(3) == D, "k/v head dim must match q");
+    TORCH_CHECK(k.size(2) == S, "kv length mismatch");
+    TORCH_CHECK(Hkv > 0 && H % Hkv == 0, "GQA requires H % Hkv == 0");
+    TORCH_CHECK(d_o.sizes() == q.sizes(), "d_o must be [B, H, S, D] like q");
+    TORCH_CHECK(lse.dim() == 3 && lse.size(0) == B && lse.size(1) == H
+                && lse.size(2) == S, "lse must be [B, H, S]");
+    TORCH_CHECK(delta.sizes() == lse.sizes(), "delta must be [B, H, S]");
     TORCH_CHECK(S % RBLK == 0, "sequence length must be a multiple of 128");
     auto qc = q.contiguous(), kc = k.contiguous(), vc = v.contiguous();
     auto doc = d_o.contiguous();
