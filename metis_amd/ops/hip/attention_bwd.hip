@@ -1,16 +1,19 @@
 // Flash attention backward for gfx950 (causal, GQA) — bf16 I/O, fp32
 // accumulation, MFMA 16x16x32, LSE-based recompute.
 //
-// v2 structure (mirrors attention.hip's forward):
+// Structure (mirrors attention.hip's forward; pieces from attn_tile.h):
 //   * split dQ / dKV kernels (deterministic, no atomics); GQA dK/dV come
 //     back per q-head and the wrapper reduces the group;
-//   * block = 256 threads = 4 waves; each wave owns TWO 16-row blocks
-//     paired (w, 7-w) so causal work balances across waves;
-//   * opposing-side tiles are 64 wide; natural-layout A/B fragments read
-//     straight from global (the 16-32 KB tiles stay L2-hot), transposed
-//     operands (K^T for dQ; Q^T / dO^T for dK, dV) staged into padded LDS
-//     with the async T14 split: the next tile's chunks load to registers
-//     under the current tile's compute;
+//   * dQ: block = 4 waves over 128 q rows, each wave owning TWO 16-row
+//     blocks paired (w, 7-w) so causal work balances across waves; dKV:
+//     one 16-row kv block per wave, 4 waves (8 at D = 64);
+//   * own-side fragments (Q, dO for dQ; K, V for dKV) are read once from
+//     global into registers; opposing-side tiles are 64 rows, staged into
+//     LDS as NATURAL padded images (K, V for dQ; Q, dO for dKV) with the
+//     T14 split: the next tile's chunks load to registers under the
+//     current tile's compute. The same image feeds the plain B-fragment
+//     reads (QK^T, dO V^T) and the ds_read_b64_tr_b16 B-fragments (dS K;
+//     dS^T Q, P^T dO) — no transposed copy exists;
 //   * dS / P^T redistribute through per-wave LDS (raw bf16 bits as
 //     shorts), published by a wave-local compiler fence — DS ops of one
 //     wave complete in order;
@@ -25,53 +28,40 @@
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
 
-#include "common.h"
+#include "attn_host.h"
+#include "attn_tile.h"
 
 namespace {
 
-typedef short short4v __attribute__((ext_vector_type(4)));
+using namespace attn_tile;
 
 constexpr int THREADS = 256;
-constexpr int RBLK = 128;    // own-side rows per block (2 x 16 per wave)
-constexpr int CTILE = 64;    // opposing-side tile width
-constexpr int VPAD = 8;      // transposed-tile row padding (bf16)
-constexpr int DMAX = 128;
+constexpr int RBLK = 128;    // dQ: q rows per block (2 x 16 per wave)
+constexpr int CTILE = 64;    // opposing-side tile rows
+constexpr int VROW = CTILE + VPAD;   // per-wave dS / P^T tile row length
+// Waves/SIMD asked of __launch_bounds__ = blocks/CU the LDS is sized for (the
+// eight-wave D=64 dKV block reaches 4 waves/SIMD, so two of it fit as well).
+constexpr int RESIDENT = 2;
+static_assert(RBLK == ATTN_SEQ_TILE, "check_attn_qkv pins S to this tile");
 
-// B-fragment via ds_read_b64_tr_b16 from a NATURAL [row][KSLOT*8] LDS
-// image: per 16-lane group, two reads cover the 8 opposing-index rows;
-// lane l&15 receives its d-column (semantics pinned by ext.tr16_probe).
-template <int KSLOT>
-__device__ __forceinline__ bf16x8 tr16_frag(
-    const short* img, int row0, int col0, int p4) {
-    bf16x8 out;
-    #pragma unroll
-    for (int r = 0; r < 2; ++r) {
-        const int row = row0 + 4 * r + (p4 >> 2);
-        const int col = col0 + (p4 & 3) * 4;
-        short4v t = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-            (__attribute__((address_space(3))) short4v*)(
-                img + row * KSLOT * 8 + col));
-        out[r * 4 + 0] = t[0];
-        out[r * 4 + 1] = t[1];
-        out[r * 4 + 2] = t[2];
-        out[r * 4 + 3] = t[3];
-    }
-    return out;
-}
-
+// dKV: kv rows per block, one 16-row block per wave
 template <int D>
-__device__ __forceinline__ bf16x8 frag8(const bf16* base, long row, int d0) {
-    if (d0 < D)
-        return *reinterpret_cast<const bf16x8*>(base + row * D + d0);
-    bf16x8 z;
-    #pragma unroll
-    for (int i = 0; i < 8; ++i) z[i] = 0;
-    return z;
-}
+constexpr int dkv_rows() { return D == 64 ? 128 : 64; }
+
+// LDS. dQ: K and V images, dS tiles [4 waves][2 row blocks][16][VROW];
+// dKV: Q and dO images, dS^T tiles [NW][16][VROW] then P^T tiles likewise.
+template <int D>
+using DqLayout = TileLayout<D, CTILE, THREADS / 64 * 2, RESIDENT>;
+template <int D>
+using DkvLayout = TileLayout<D, CTILE, 2 * (dkv_rows<D>() / 16), RESIDENT>;
+static_assert(DqLayout<64>::bytes == 36864 && DqLayout<80>::bytes == 40960
+              && DqLayout<96>::bytes == 45056 && DqLayout<128>::bytes == 53248);
+static_assert(DkvLayout<64>::bytes == 55296 && DkvLayout<80>::bytes == 40960
+              && DkvLayout<96>::bytes == 45056 && DkvLayout<128>::bytes == 53248);
 
 // ---------------------------------------------------------------- dQ ----
 template <int D>
-__global__ __launch_bounds__(THREADS, 2) void attn_bwd_dq_kernel(
+__global__ __launch_bounds__(THREADS, RESIDENT) void attn_bwd_dq_kernel(
     const bf16* __restrict__ Q, const bf16* __restrict__ K,
     const bf16* __restrict__ V, const bf16* __restrict__ dO,
     const float* __restrict__ LSE, const float* __restrict__ Delta,
@@ -82,26 +72,21 @@ __global__ __launch_bounds__(THREADS, 2) void attn_bwd_dq_kernel(
     const int col16 = lane & 15;
     const int k8 = lane >> 4;
 
-    constexpr int dchunks = (D + 31) / 32;
-    constexpr int djtiles = D / 16;
-    constexpr int VROW = CTILE + VPAD;
+    using L = DqLayout<D>;
+    constexpr int dchunks = Geom<D>::dchunks;
+    constexpr int djtiles = Geom<D>::djtiles;
+    constexpr int KSLOT = Geom<D>::KSLOT;
 
-    const int qtile = blockIdx.x % (S / RBLK);
-    const int head = (blockIdx.x / (S / RBLK)) % H;
-    const int batch = blockIdx.x / (S / RBLK) / H;
-    const int kv_head = head / (H / Hkv);
-    const long q_base = (((long)batch * H + head) * S) * D;
-    const long kv_base = (((long)batch * Hkv + kv_head) * S) * D;
-    const long row_base = ((long)batch * H + head) * S;
+    const BlockCoord bc = block_coord<D>(S / RBLK, H, Hkv, S);
+    const long q_base = bc.q_base, row_base = bc.row_base;
 
     const int rbid[2] = {wave, 7 - wave};
-    const int qb = qtile * RBLK;
+    const int qb = bc.tile * RBLK;
 
-    constexpr int KSLOT = D / 8 + 1;    // natural-tile slots per row (padded)
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    short* Ks = reinterpret_cast<short*>(smem);                    // [CTILE][KSLOT*8]
-    short* Vs = Ks + CTILE * KSLOT * 8;                            // [CTILE][KSLOT*8]
-    short* Sw = Vs + CTILE * KSLOT * 8 + wave * 2 * 16 * VROW;     // [2][16][VROW]
+    short* Ks = reinterpret_cast<short*>(smem) + L::a_off;
+    short* Vs = reinterpret_cast<short*>(smem) + L::b_off;
+    short* Sw = reinterpret_cast<short*>(smem) + L::w_off + wave * 2 * L::w_tile;
 
     // per-row state and Q/dO fragments for both row blocks
     float lse_r[2][4], delta_r[2][4];
@@ -121,47 +106,21 @@ __global__ __launch_bounds__(THREADS, 2) void attn_bwd_dq_kernel(
         }
     }
 
-    floatx4 dq_acc[2][djtiles];
-    #pragma unroll
-    for (int rb = 0; rb < 2; ++rb)
-        #pragma unroll
-        for (int jd = 0; jd < djtiles; ++jd)
-            dq_acc[rb][jd] = floatx4{0.f, 0.f, 0.f, 0.f};
+    floatx4 dq_acc[2][djtiles] = {};
 
-    // T14 staged K (reused for the natural tile AND the transpose) plus
-    // a direct-staged natural V tile; kv-row-major lane walk keeps the
-    // transpose writes conflict-free
-    constexpr int chunks = CTILE * D / 8;
-    constexpr int per_thread = (chunks + THREADS - 1) / THREADS;
-    bf16x8 k_stage[per_thread];
-    auto issue_loads = [&](int kv0) {
-        #pragma unroll
-        for (int u = 0; u < per_thread; ++u) {
-            const int c = threadIdx.x + u * THREADS;
-            if (c >= chunks) break;
-            k_stage[u] = *reinterpret_cast<const bf16x8*>(
-                K + kv_base + (long)(kv0 + c % CTILE) * D + (c / CTILE) * 8);
-        }
-    };
-    auto write_stage = [&](int kv0) {
-        #pragma unroll
-        for (int u = 0; u < per_thread; ++u) {
-            const int c = threadIdx.x + u * THREADS;
-            if (c >= chunks) break;
-            const int row = c % CTILE;
-            const int d0 = (c / CTILE) * 8;
-            *reinterpret_cast<bf16x8*>(Ks + row * KSLOT * 8 + d0) = k_stage[u];
-            bf16x8 vv = *reinterpret_cast<const bf16x8*>(
-                V + kv_base + (long)(kv0 + row) * D + d0);
-            *reinterpret_cast<bf16x8*>(Vs + row * KSLOT * 8 + d0) = vv;
-        }
-    };
+    // T14 staged K (one natural image serves the QK^T reads and the tr16
+    // reads of dS K); V has no stage registers and is loaded when its
+    // natural image is written. Lanes walk kv rows for both.
+    TileStage<CTILE, D, THREADS, Walk::RowsInDChunk, Walk::RowsInDChunk,
+              /*STAGE_B=*/false> stage;
+    const bf16* Kh = K + bc.kv_base;
+    const bf16* Vh = V + bc.kv_base;
 
     const int kv_end = qb + RBLK;
-    issue_loads(0);
+    stage.issue_loads(Kh, Vh, 0);
     for (int kv0 = 0; kv0 < kv_end; kv0 += CTILE) {
-        write_stage(kv0);
-        if (kv0 + CTILE < kv_end) issue_loads(kv0 + CTILE);
+        stage.write_stage(Ks, Vs, Vh, kv0);
+        if (kv0 + CTILE < kv_end) stage.issue_loads(Kh, Vh, kv0 + CTILE);
         __syncthreads();
 
         bool rb_active[2];
@@ -182,15 +141,7 @@ __global__ __launch_bounds__(THREADS, 2) void attn_bwd_dq_kernel(
                 for (int c = 0; c < dchunks; ++c) {
                     const int d0 = c * 32 + k8 * 8;
                     bf16x8 kf, vf;
-                    if (d0 < D) {
-                        kf = *reinterpret_cast<const bf16x8*>(
-                            Ks + kvrow * KSLOT * 8 + d0);
-                        vf = *reinterpret_cast<const bf16x8*>(
-                            Vs + kvrow * KSLOT * 8 + d0);
-                    } else {
-                        #pragma unroll
-                        for (int i = 0; i < 8; ++i) { kf[i] = 0; vf[i] = 0; }
-                    }
+                    lds_frag2<D, KSLOT>(Ks, Vs, kvrow, d0, kf, vf);
                     s_acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
                         q_frag[rb][c], kf, s_acc[j], 0, 0, 0);
                     dp_acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
@@ -222,7 +173,6 @@ __global__ __launch_bounds__(THREADS, 2) void attn_bwd_dq_kernel(
         for (int rb = 0; rb < 2; ++rb) {
             if (!rb_active[rb]) continue;
             const short* Srb = Sw + rb * 16 * VROW;
-            const int p4 = lane & 15;
             #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
                 bf16x8 ds_frag = *reinterpret_cast<const bf16x8*>(
@@ -230,7 +180,7 @@ __global__ __launch_bounds__(THREADS, 2) void attn_bwd_dq_kernel(
                 #pragma unroll
                 for (int jd = 0; jd < djtiles; ++jd) {
                     bf16x8 kt_frag = tr16_frag<KSLOT>(
-                        Ks, ks * 32 + k8 * 8, jd * 16, p4);
+                        Ks, ks * 32 + k8 * 8, jd * 16, col16);
                     dq_acc[rb][jd] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
                         ds_frag, kt_frag, dq_acc[rb][jd], 0, 0, 0);
                 }
@@ -260,7 +210,7 @@ __global__ __launch_bounds__(THREADS, 2) void attn_bwd_dq_kernel(
 // VGPR footprints lose the second independent block's latency
 // cover), so those stay 4-wave x 64 rows.
 template <int D>
-__global__ __launch_bounds__(D == 64 ? 2 * THREADS : THREADS, 2)
+__global__ __launch_bounds__(dkv_rows<D>() / 16 * 64, RESIDENT)
 void attn_bwd_dkv_kernel(
     const bf16* __restrict__ Q, const bf16* __restrict__ K,
     const bf16* __restrict__ V, const bf16* __restrict__ dO,
@@ -273,34 +223,25 @@ void attn_bwd_dkv_kernel(
     const int col16 = lane & 15;
     const int k8 = lane >> 4;
 
-    constexpr int dchunks = (D + 31) / 32;
-    constexpr int djtiles = D / 16;
-    constexpr int VROW = CTILE + VPAD;
-    constexpr int KSLOT = D / 8 + 1;
-    constexpr int KVB = D == 64 ? 128 : 64;  // kv rows per block
+    using L = DkvLayout<D>;
+    constexpr int dchunks = Geom<D>::dchunks;
+    constexpr int djtiles = Geom<D>::djtiles;
+    constexpr int KSLOT = Geom<D>::KSLOT;
+    constexpr int KVB = dkv_rows<D>();
     constexpr int NW = KVB / 16;             // waves per block
 
-    const int kvtile = blockIdx.x % (S / KVB);
-    const int head = (blockIdx.x / (S / KVB)) % H;
-    const int batch = blockIdx.x / (S / KVB) / H;
-    const int kv_head = head / (H / Hkv);
-    const long q_base = (((long)batch * H + head) * S) * D;
-    const long kv_base = (((long)batch * Hkv + kv_head) * S) * D;
-    const long out_base = (((long)batch * H + head) * S) * D;
-    const long row_base = ((long)batch * H + head) * S;
+    const BlockCoord bc = block_coord<D>(S / KVB, H, Hkv, S);
+    const long kv_base = bc.kv_base, row_base = bc.row_base;
+    const long out_base = bc.q_base;      // dK/dV come back per q-head
 
-    const int kv0 = kvtile * KVB + wave * 16;   // this wave's kv rows
+    const int kv0 = bc.tile * KVB + wave * 16;   // this wave's kv rows
 
-    // Natural Q/dO LDS images only: the dK/dV B-fragments come from
-    // ds_read_b64_tr_b16 straight off these, so the scalar-transposed
-    // Qt/dOt copies (and their LDS staging writes) are gone; the freed
-    // LDS restores 2 blocks/CU at every D.
+    // natural Q/dO images only: dK/dV B-fragments are tr16 reads off these
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    short* Qs = reinterpret_cast<short*>(smem);                    // [CTILE][KSLOT*8]
-    short* dOs = Qs + CTILE * KSLOT * 8;                           // [CTILE][KSLOT*8]
-    short* Sw = dOs + CTILE * KSLOT * 8 + wave * 16 * VROW;        // [16][VROW]
-    short* Pw = dOs + CTILE * KSLOT * 8 + NW * 16 * VROW
-                + wave * 16 * VROW;                                // [16][VROW]
+    short* Qs = reinterpret_cast<short*>(smem) + L::a_off;
+    short* dOs = reinterpret_cast<short*>(smem) + L::b_off;
+    short* Sw = reinterpret_cast<short*>(smem) + L::w_off + wave * L::w_tile;
+    short* Pw = reinterpret_cast<short*>(smem) + L::w_off + (NW + wave) * L::w_tile;
 
     // K and V fragments for this wave's rows (A layout, m = col16)
     bf16x8 k_frag[dchunks], v_frag[dchunks];
@@ -310,57 +251,22 @@ void attn_bwd_dkv_kernel(
         v_frag[c] = frag8<D>(V + kv_base, kv0 + col16, c * 32 + k8 * 8);
     }
 
-    floatx4 dk_acc[djtiles], dv_acc[djtiles];
-    #pragma unroll
-    for (int jd = 0; jd < djtiles; ++jd) {
-        dk_acc[jd] = floatx4{0.f, 0.f, 0.f, 0.f};
-        dv_acc[jd] = floatx4{0.f, 0.f, 0.f, 0.f};
-    }
+    floatx4 dk_acc[djtiles] = {}, dv_acc[djtiles] = {};
 
-    // T14 staged Q and dO (each register set feeds both the natural and
-    // transposed LDS image); at D=128 the dO set would spill past 256
-    // VGPRs on top of the dK+dV accumulators, so dO stages direct there.
-    constexpr int NT = NW * 64;         // staging threads
-    constexpr int chunks = CTILE * D / 8;
-    constexpr int per_thread = (chunks + NT - 1) / NT;
+    // T14 staged Q and dO, all NW waves staging, lanes walking q rows. At
+    // D=128 the dO set would spill past 256 VGPRs on top of the dK+dV
+    // accumulators, so dO is loaded at write time there.
     constexpr bool STAGE_DO = (D <= 96);
-    bf16x8 q_stage[per_thread];
-    bf16x8 do_stage[STAGE_DO ? per_thread : 1];
-    auto issue_loads = [&](int q0) {
-        #pragma unroll
-        for (int u = 0; u < per_thread; ++u) {
-            const int c = threadIdx.x + u * NT;
-            if (c >= chunks) break;
-            q_stage[u] = *reinterpret_cast<const bf16x8*>(
-                Q + q_base + (long)(q0 + c % CTILE) * D + (c / CTILE) * 8);
-            if constexpr (STAGE_DO)
-                do_stage[u] = *reinterpret_cast<const bf16x8*>(
-                    dO + q_base + (long)(q0 + c % CTILE) * D + (c / CTILE) * 8);
-        }
-    };
-    auto write_stage = [&](int q0) {
-        #pragma unroll
-        for (int u = 0; u < per_thread; ++u) {
-            const int c = threadIdx.x + u * NT;
-            if (c >= chunks) break;
-            const int row = c % CTILE;
-            const int d0 = (c / CTILE) * 8;
-            *reinterpret_cast<bf16x8*>(Qs + row * KSLOT * 8 + d0) = q_stage[u];
-            bf16x8 dov;
-            if constexpr (STAGE_DO)
-                dov = do_stage[u];
-            else
-                dov = *reinterpret_cast<const bf16x8*>(
-                    dO + q_base + (long)(q0 + row) * D + d0);
-            *reinterpret_cast<bf16x8*>(dOs + row * KSLOT * 8 + d0) = dov;
-        }
-    };
+    TileStage<CTILE, D, NW * 64, Walk::RowsInDChunk, Walk::RowsInDChunk,
+              STAGE_DO> stage;
+    const bf16* Qh = Q + bc.q_base;
+    const bf16* dOh = dO + bc.q_base;
 
-    const int q_start = kvtile * KVB;   // causal: from the block's kv start
-    issue_loads(q_start);
+    const int q_start = bc.tile * KVB;   // causal: from the block's kv start
+    stage.issue_loads(Qh, dOh, q_start);
     for (int q0 = q_start; q0 < S; q0 += CTILE) {
-        write_stage(q0);
-        if (q0 + CTILE < S) issue_loads(q0 + CTILE);
+        stage.write_stage(Qs, dOs, dOh, q0);
+        if (q0 + CTILE < S) stage.issue_loads(Qh, dOh, q0 + CTILE);
         __syncthreads();
 
         const bool active = q0 + CTILE - 1 >= kv0;
@@ -376,15 +282,7 @@ void attn_bwd_dkv_kernel(
                 for (int c = 0; c < dchunks; ++c) {
                     const int d0 = c * 32 + k8 * 8;
                     bf16x8 qf, dof;
-                    if (d0 < D) {
-                        qf = *reinterpret_cast<const bf16x8*>(
-                            Qs + qrow * KSLOT * 8 + d0);
-                        dof = *reinterpret_cast<const bf16x8*>(
-                            dOs + qrow * KSLOT * 8 + d0);
-                    } else {
-                        #pragma unroll
-                        for (int i = 0; i < 8; ++i) { qf[i] = 0; dof[i] = 0; }
-                    }
+                    lds_frag2<D, KSLOT>(Qs, dOs, qrow, d0, qf, dof);
                     st_acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
                         k_frag[c], qf, st_acc[j], 0, 0, 0);
                     dpt_acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
@@ -413,7 +311,6 @@ void attn_bwd_dkv_kernel(
 
             asm volatile("" ::: "memory");   // wave-local publish
 
-            const int p4 = lane & 15;
             #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
                 bf16x8 dst_frag = *reinterpret_cast<const bf16x8*>(
@@ -423,11 +320,11 @@ void attn_bwd_dkv_kernel(
                 #pragma unroll
                 for (int jd = 0; jd < djtiles; ++jd) {
                     bf16x8 qt_frag = tr16_frag<KSLOT>(
-                        Qs, ks * 32 + k8 * 8, jd * 16, p4);
+                        Qs, ks * 32 + k8 * 8, jd * 16, col16);
                     dk_acc[jd] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
                         dst_frag, qt_frag, dk_acc[jd], 0, 0, 0);
                     bf16x8 dot_frag = tr16_frag<KSLOT>(
-                        dOs, ks * 32 + k8 * 8, jd * 16, p4);
+                        dOs, ks * 32 + k8 * 8, jd * 16, col16);
                     dv_acc[jd] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
                         pt_frag, dot_frag, dv_acc[jd], 0, 0, 0);
                 }
@@ -501,8 +398,7 @@ torch::Tensor attn_bwd_delta(torch::Tensor o, torch::Tensor d_o) {
     TORCH_CHECK(o.is_contiguous() && d_o.is_contiguous(),
                 "o and d_o must be contiguous");
     const long D = o.size(3);
-    TORCH_CHECK(D == 64 || D == 80 || D == 96 || D == 128,
-                "head dim must be 64/80/96/128, got ", D);
+    check_head_dim(D);
     const long rows = o.numel() / D;
     auto delta = torch::empty({o.size(0), o.size(1), o.size(2)},
                               o.options().dtype(torch::kFloat32));
@@ -522,81 +418,46 @@ std::vector<torch::Tensor> attn_bwd(
     torch::Tensor q, torch::Tensor k, torch::Tensor v,
     torch::Tensor d_o, torch::Tensor lse, torch::Tensor delta,
     double scale) {
-    TORCH_CHECK(q.is_cuda() && q.dtype() == torch::kBFloat16, "q must be CUDA bf16");
-    TORCH_CHECK(q.dim() == 4, "q must be [B, H, S, D]");
-    const long B = q.size(0), H = q.size(1), S = q.size(2), D = q.size(3);
-    TORCH_CHECK(k.is_cuda() && k.dtype() == torch::kBFloat16
-                && v.is_cuda() && v.dtype() == torch::kBFloat16
-                && d_o.is_cuda() && d_o.dtype() == torch::kBFloat16,
-                "k, v and d_o must be CUDA bf16");
+    const AttnDims a = check_attn_qkv(q, k, v);
+    TORCH_CHECK(d_o.is_cuda() && d_o.dtype() == torch::kBFloat16,
+                "d_o must be CUDA bf16");
     TORCH_CHECK(lse.is_cuda() && lse.dtype() == torch::kFloat32
                 && delta.is_cuda() && delta.dtype() == torch::kFloat32,
                 "lse and delta must be CUDA fp32");
-    for (const torch::Tensor* t : {&k, &v, &d_o, &lse, &delta})
+    for (const torch::Tensor* t : {&d_o, &lse, &delta})
         TORCH_CHECK(t->get_device() == q.get_device(),
                     "all attn_bwd arguments must be on the same device");
-    TORCH_CHECK(k.dim() == 4 && v.dim() == 4 && k.sizes() == v.sizes(),
-                "k and v must both be [B, Hkv, S, D]");
-    const long Hkv = k.size(1);
-    TORCH_CHECK(k.size(0) == B, "k/v batch must match q");
-    TORCH_CHECK(k.size(3) == D, "k/v head dim must match q");
-    TORCH_CHECK(k.size(2) == S, "kv length mismatch");
-    TORCH_CHECK(Hkv > 0 && H % Hkv == 0, "GQA requires H % Hkv == 0");
     TORCH_CHECK(d_o.sizes() == q.sizes(), "d_o must be [B, H, S, D] like q");
-    TORCH_CHECK(lse.dim() == 3 && lse.size(0) == B && lse.size(1) == H
-                && lse.size(2) == S, "lse must be [B, H, S]");
+    TORCH_CHECK(lse.dim() == 3 && lse.size(0) == a.B && lse.size(1) == a.H
+                && lse.size(2) == a.S, "lse must be [B, H, S]");
     TORCH_CHECK(delta.sizes() == lse.sizes(), "delta must be [B, H, S]");
-    TORCH_CHECK(S % RBLK == 0, "sequence length must be a multiple of 128");
     auto qc = q.contiguous(), kc = k.contiguous(), vc = v.contiguous();
     auto doc = d_o.contiguous();
     auto lsec = lse.contiguous(), dc = delta.contiguous();
 
     auto dq = torch::empty_like(qc);
-    auto dk = torch::empty({B, H, S, D}, q.options());
-    auto dv = torch::empty({B, H, S, D}, q.options());
+    auto dk = torch::empty({a.B, a.H, a.S, a.D}, q.options());
+    auto dv = torch::empty({a.B, a.H, a.S, a.D}, q.options());
 
     auto stream = c10::hip::getCurrentHIPStream().stream();
-    const int grid = (int)(B * H * (S / RBLK));
-    // dkv grid: one block per KVB kv rows (KVB is 128 at D=64, 64 else)
-
-    #define LAUNCH_BWD(DD)                                                    \
-        do {                                                                  \
-            const int vrow = CTILE + VPAD;                                    \
-            const int lds_dq = (2 * CTILE * (DD / 8 + 1) * 8                  \
-                                + DD * vrow + 4 * 2 * 16 * vrow) * 2;         \
-            const int nw_dkv = (DD == 64) ? 8 : 4;                            \
-            const int lds_dkv = (2 * CTILE * (DD / 8 + 1) * 8                 \
-                                 + 2 * nw_dkv * 16 * vrow) * 2;               \
-            hipLaunchKernelGGL(attn_bwd_dq_kernel<DD>, dim3(grid),            \
-                dim3(THREADS), lds_dq, stream,                                \
-                reinterpret_cast<const bf16*>(qc.data_ptr()),                 \
-                reinterpret_cast<const bf16*>(kc.data_ptr()),                 \
-                reinterpret_cast<const bf16*>(vc.data_ptr()),                 \
-                reinterpret_cast<const bf16*>(doc.data_ptr()),                \
-                lsec.data_ptr<float>(), dc.data_ptr<float>(),                 \
-                reinterpret_cast<bf16*>(dq.data_ptr()),                       \
-                (int)B, (int)H, (int)Hkv, (int)S, (float)scale);              \
-            const int kvb_dkv = (DD == 64) ? 128 : 64;                        \
-            const int grid_dkv = (int)(B * H * (S / kvb_dkv));                \
-            hipLaunchKernelGGL(attn_bwd_dkv_kernel<DD>, dim3(grid_dkv),       \
-                dim3((DD == 64) ? 2 * THREADS : THREADS), lds_dkv, stream,    \
-                reinterpret_cast<const bf16*>(qc.data_ptr()),                 \
-                reinterpret_cast<const bf16*>(kc.data_ptr()),                 \
-                reinterpret_cast<const bf16*>(vc.data_ptr()),                 \
-                reinterpret_cast<const bf16*>(doc.data_ptr()),                \
-                lsec.data_ptr<float>(), dc.data_ptr<float>(),                 \
-                reinterpret_cast<bf16*>(dk.data_ptr()),                       \
-                reinterpret_cast<bf16*>(dv.data_ptr()),                       \
-                (int)B, (int)H, (int)Hkv, (int)S, (float)scale);              \
-        } while (0)
-    switch ((int)D) {
-        case 64: LAUNCH_BWD(64); break;
-        case 80: LAUNCH_BWD(80); break;
-        case 96: LAUNCH_BWD(96); break;
-        case 128: LAUNCH_BWD(128); break;
-        default: TORCH_CHECK(false, "head dim must be 64/80/96/128, got ", D);
-    }
-    #undef LAUNCH_BWD
+    dispatch_head_dim(a.D, [&](auto d) {
+        constexpr int DD = decltype(d)::value;
+        const int grid_dq = (int)(a.B * a.H * (a.S / RBLK));
+        hipLaunchKernelGGL(attn_bwd_dq_kernel<DD>, dim3(grid_dq),
+            dim3(THREADS), DqLayout<DD>::bytes, stream,
+            bf16_ptr(qc), bf16_ptr(kc), bf16_ptr(vc), bf16_ptr(doc),
+            lsec.data_ptr<float>(), dc.data_ptr<float>(), bf16_ptr(dq),
+            (int)a.B, (int)a.H, (int)a.Hkv, (int)a.S, (float)scale);
+        // one block per dkv_rows kv rows, one wave per 16 of them
+        constexpr int KVB = dkv_rows<DD>();
+        const int grid_dkv = (int)(a.B * a.H * (a.S / KVB));
+        hipLaunchKernelGGL(attn_bwd_dkv_kernel<DD>, dim3(grid_dkv),
+            dim3(KVB / 16 * 64), DkvLayout<DD>::bytes, stream,
+            bf16_ptr(qc), bf16_ptr(kc), bf16_ptr(vc), bf16_ptr(doc),
+            lsec.data_ptr<float>(), dc.data_ptr<float>(),
+            bf16_ptr(dk), bf16_ptr(dv),
+            (int)a.B, (int)a.H, (int)a.Hkv, (int)a.S, (float)scale);
+    });
     HIP_CHECK_LAST();
     return {dq, dk, dv};
 }

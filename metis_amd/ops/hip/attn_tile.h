@@ -1,0 +1,183 @@
+// Tile toolkit shared by the MFMA attention kernels (attention.hip forward,
+// attention_bwd.hip dQ and dKV): per-D geometry, the dynamic-LDS layout,
+// fragment reads, the block-coordinate decode and the register-staged
+// (T14) tile copy. A new attention kernel starts from these pieces
+// (docs/KERNELS.md). All __forceinline__ / constexpr: no scratch.
+#pragma once
+
+#include "common.h"
+
+namespace attn_tile {
+
+typedef short short4v __attribute__((ext_vector_type(4)));
+
+constexpr int VPAD = 8;                 // per-wave P / dS tile row padding (bf16)
+constexpr int LDS_PER_CU = 160 * 1024;
+
+// Per-D geometry. LDS tiles are NATURAL [row][D] images of raw bf16 bits
+// (shorts), each row padded by one 16-B slot so the power-of-2 row stride
+// does not land every row on the same banks.
+template <int D>
+struct Geom {
+    static constexpr int dchunks = (D + 31) / 32;   // 32-wide MFMA K chunks of D
+    static constexpr int djtiles = D / 16;          // 16-wide output column tiles
+    static constexpr int KSLOT = D / 8 + 1;         // 16-B slots per LDS row
+    static constexpr int tile(int rows) { return rows * KSLOT * 8; }   // shorts
+};
+
+// Dynamic-LDS layout all three kernels instantiate, offsets in shorts: two
+// natural [ROWS][D] images (A, B) and WTILES per-wave [16][ROWS + VPAD]
+// tiles (P, dS, P^T). The kernel carves its pointers from the offsets and
+// its launcher requests `bytes`, so the two cannot disagree.
+template <int D, int ROWS, int WTILES, int RESIDENT>
+struct TileLayout {
+    static constexpr int WROW = ROWS + VPAD;
+    static constexpr int a_off = 0;
+    static constexpr int b_off = Geom<D>::tile(ROWS);
+    static constexpr int w_off = 2 * Geom<D>::tile(ROWS);
+    static constexpr int w_tile = 16 * WROW;
+    static constexpr int bytes = (w_off + WTILES * w_tile) * 2;
+    // b128 accesses need 16-B alignment; a tr16 read off it returns wrong data
+    static_assert(b_off % 8 == 0 && w_off % 8 == 0 && w_tile % 8 == 0);
+    static_assert(bytes * RESIDENT <= LDS_PER_CU, "resident blocks must fit one CU");
+};
+
+// A/B fragment (8 bf16 of row `row` at column d0) straight from global;
+// zero where a 32-wide chunk runs past D (D = 80).
+template <int D>
+__device__ __forceinline__ bf16x8 frag8(const bf16* base, long row, int d0) {
+    if (d0 < D)
+        return *reinterpret_cast<const bf16x8*>(base + row * D + d0);
+    return bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+}
+
+// The same fragment from a natural [row][KSLOT*8] LDS image.
+template <int D, int KSLOT>
+__device__ __forceinline__ bf16x8 lds_frag(const short* img, int row, int d0) {
+    if (d0 < D)
+        return *reinterpret_cast<const bf16x8*>(img + row * KSLOT * 8 + d0);
+    return bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+}
+
+// Two images read at the same (row, d0) under ONE tail guard: two separate
+// lds_frag calls compile to two exec-masked regions at D = 80.
+template <int D, int KSLOT>
+__device__ __forceinline__ void lds_frag2(const short* img_a, const short* img_b,
+                                          int row, int d0, bf16x8& a, bf16x8& b) {
+    a = b = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+    if (d0 < D) {
+        a = *reinterpret_cast<const bf16x8*>(img_a + row * KSLOT * 8 + d0);
+        b = *reinterpret_cast<const bf16x8*>(img_b + row * KSLOT * 8 + d0);
+    }
+}
+
+// B-fragment via ds_read_b64_tr_b16 from a NATURAL [row][KSLOT*8] LDS
+// image: per 16-lane group, two reads cover the 8 opposing-index rows;
+// lane l&15 receives its d-column (semantics pinned by ext.tr16_probe).
+template <int KSLOT>
+__device__ __forceinline__ bf16x8 tr16_frag(
+    const short* img, int row0, int col0, int p4) {
+    bf16x8 out;
+    #pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const int row = row0 + 4 * r + (p4 >> 2);
+        const int col = col0 + (p4 & 3) * 4;
+        short4v t = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+            (__attribute__((address_space(3))) short4v*)(
+                img + row * KSLOT * 8 + col));
+        out[r * 4 + 0] = t[0];
+        out[r * 4 + 1] = t[1];
+        out[r * 4 + 2] = t[2];
+        out[r * 4 + 3] = t[3];
+    }
+    return out;
+}
+
+// blockIdx.x = (batch * H + head) * tiles + tile: the tile index and the
+// offsets of that q head and of its GQA kv head.
+struct BlockCoord {
+    int tile;
+    long q_base, kv_base;   // element offsets into [B, H|Hkv, S, D]
+    long row_base;          // row offset into [B, H, S]
+};
+
+template <int D>
+__device__ __forceinline__ BlockCoord block_coord(int tiles, int H, int Hkv, int S) {
+    const int head = (blockIdx.x / tiles) % H;
+    const int batch = blockIdx.x / tiles / H;
+    const int kv_head = head / (H / Hkv);
+    BlockCoord c;
+    c.tile = blockIdx.x % tiles;
+    c.row_base = ((long)batch * H + head) * S;
+    c.q_base = c.row_base * D;
+    c.kv_base = (((long)batch * Hkv + kv_head) * S) * D;
+    return c;
+}
+
+// How consecutive 16-B chunk indices (= consecutive lanes) walk a
+// [ROWS][D] tile: along a row first, or down the rows of one d-chunk.
+enum class Walk { DChunksInRow, RowsInDChunk };
+
+template <int ROWS, int D, Walk W>
+__device__ __forceinline__ void chunk_pos(int c, int& row, int& d0) {
+    if constexpr (W == Walk::DChunksInRow) {
+        row = c / (D / 8);
+        d0 = c % (D / 8) * 8;
+    } else {
+        row = c % ROWS;
+        d0 = c / ROWS * 8;
+    }
+}
+
+// T14 register-staged copy of two [ROWS][D] global tiles (A, B) into
+// natural LDS images by NT threads: issue_loads() one tile AHEAD (HBM
+// latency hides under the current tile's compute), write_stage() at loop
+// top. With STAGE_B false B has no registers and is loaded at write time.
+template <int ROWS, int D, int NT, Walk WA, Walk WB, bool STAGE_B = true>
+struct TileStage {
+    static constexpr int chunks = ROWS * D / 8;     // 16-B chunks per tile
+    static constexpr int per_thread = (chunks + NT - 1) / NT;
+
+    bf16x8 a[per_thread];
+    bf16x8 b[STAGE_B ? per_thread : 1];
+
+    template <Walk W>
+    static __device__ __forceinline__ bf16x8 load(const bf16* src, int row0, int c) {
+        int row, d0;
+        chunk_pos<ROWS, D, W>(c, row, d0);
+        return *reinterpret_cast<const bf16x8*>(src + (long)(row0 + row) * D + d0);
+    }
+    template <Walk W>
+    static __device__ __forceinline__ void store(short* img, int c, bf16x8 val) {
+        int row, d0;
+        chunk_pos<ROWS, D, W>(c, row, d0);
+        *reinterpret_cast<bf16x8*>(img + Geom<D>::tile(row) + d0) = val;
+    }
+
+    // A and B point at row 0 of this head; row0 is the tile's first row
+    __device__ __forceinline__ void issue_loads(
+        const bf16* A, const bf16* B, int row0) {
+        #pragma unroll
+        for (int u = 0; u < per_thread; ++u) {
+            const int c = threadIdx.x + u * NT;
+            if (c >= chunks) break;
+            a[u] = load<WA>(A, row0, c);
+            if constexpr (STAGE_B) b[u] = load<WB>(B, row0, c);
+        }
+    }
+    __device__ __forceinline__ void write_stage(
+        short* As, short* Bs, const bf16* B, int row0) {
+        #pragma unroll
+        for (int u = 0; u < per_thread; ++u) {
+            const int c = threadIdx.x + u * NT;
+            if (c >= chunks) break;
+            store<WA>(As, c, a[u]);
+            bf16x8 bv;
+            if constexpr (STAGE_B) bv = b[u];
+            else bv = load<WB>(B, row0, c);
+            store<WB>(Bs, c, bv);
+        }
+    }
+};
+
+}  // namespace attn_tile

@@ -14,7 +14,7 @@
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
 
-#include "common.h"
+#include "attn_host.h"   // brings common.h
 
 namespace {
 
@@ -117,33 +117,18 @@ __global__ __launch_bounds__(THREADS) void attn_decode_kernel(
 
 torch::Tensor attn_decode(torch::Tensor q, torch::Tensor k, torch::Tensor v,
                           double scale) {
-    TORCH_CHECK(q.is_cuda() && q.dtype() == torch::kBFloat16);
-    TORCH_CHECK(q.dim() == 4 && q.size(2) == 1, "q must be [B, H, 1, D]");
-    const long B = q.size(0), H = q.size(1), D = q.size(3);
-    const long Hkv = k.size(1), S = k.size(2);
-    TORCH_CHECK(k.size(3) == D && v.size(2) == S);
+    const AttnDims a = check_attn_qkv(q, k, v, /*decode=*/true);
     auto qc = q.contiguous(), kc = k.contiguous(), vc = v.contiguous();
     auto out = torch::empty_like(qc);
     auto stream = c10::hip::getCurrentHIPStream().stream();
-    const int grid = (int)(B * H);
+    const int grid = (int)(a.B * a.H);
 
-    #define LAUNCH_DEC(DD)                                                \
-        hipLaunchKernelGGL(attn_decode_kernel<DD>, dim3(grid),            \
-            dim3(THREADS), 0, stream,                                     \
-            reinterpret_cast<const bf16*>(qc.data_ptr()),                 \
-            reinterpret_cast<const bf16*>(kc.data_ptr()),                 \
-            reinterpret_cast<const bf16*>(vc.data_ptr()),                 \
-            reinterpret_cast<bf16*>(out.data_ptr()),                      \
-            (int)B, (int)H, (int)Hkv, (int)S, (float)scale)
-
-    switch (D) {
-        case 64: LAUNCH_DEC(64); break;
-        case 80: LAUNCH_DEC(80); break;
-        case 96: LAUNCH_DEC(96); break;
-        case 128: LAUNCH_DEC(128); break;
-        default: TORCH_CHECK(false, "unsupported head dim ", D);
-    }
-    #undef LAUNCH_DEC
+    dispatch_head_dim(a.D, [&](auto d) {
+        hipLaunchKernelGGL(attn_decode_kernel<decltype(d)::value>, dim3(grid),
+            dim3(THREADS), 0, stream,
+            bf16_ptr(qc), bf16_ptr(kc), bf16_ptr(vc), bf16_ptr(out),
+            (int)a.B, (int)a.H, (int)a.Hkv, (int)a.S, (float)scale);
+    });
     HIP_CHECK_LAST();
     return out;
 }

@@ -32,6 +32,7 @@
 
 #include <algorithm>
 
+#include "attn_host.h"
 #include "common.h"
 
 namespace {
@@ -333,33 +334,27 @@ torch::Tensor attn_decode_ragged(torch::Tensor q, torch::Tensor k,
     auto stream = c10::hip::getCurrentHIPStream().stream();
     const dim3 grid(ns, (unsigned)Hkv, (unsigned)B);
 
-    #define LAUNCH_RAG(DD, GG)                                            \
-        hipLaunchKernelGGL((attn_decode_ragged_kernel<DD, GG>), grid,     \
-            dim3(THREADS), 0, stream,                                     \
-            reinterpret_cast<const short*>(qc.data_ptr()),                \
-            reinterpret_cast<const short*>(kc.data_ptr()),                \
-            reinterpret_cast<const short*>(vc.data_ptr()),                \
-            lens.data_ptr<int>(),                                         \
-            reinterpret_cast<short*>(out.data_ptr()), acc_p, ml_p,        \
-            (int)H, (int)S, chunk, ns,                                    \
-            (long)kc.stride(0), (long)kc.stride(1),                       \
-            (long)vc.stride(0), (long)vc.stride(1), (float)scale)
-    #define LAUNCH_RAG_D(DD)                                              \
-        switch (G) {                                                      \
-            case 1: LAUNCH_RAG(DD, 1); break;                             \
-            case 2: LAUNCH_RAG(DD, 2); break;                             \
-            case 4: LAUNCH_RAG(DD, 4); break;                             \
-            default: LAUNCH_RAG(DD, 8); break;                            \
+    dispatch_head_dim(D, [&](auto d) {
+        auto launch = [&](auto g) {
+            hipLaunchKernelGGL(
+                (attn_decode_ragged_kernel<decltype(d)::value, decltype(g)::value>),
+                grid, dim3(THREADS), 0, stream,
+                reinterpret_cast<const short*>(qc.data_ptr()),
+                reinterpret_cast<const short*>(kc.data_ptr()),
+                reinterpret_cast<const short*>(vc.data_ptr()),
+                lens.data_ptr<int>(),
+                reinterpret_cast<short*>(out.data_ptr()), acc_p, ml_p,
+                (int)H, (int)S, chunk, ns,
+                (long)kc.stride(0), (long)kc.stride(1),
+                (long)vc.stride(0), (long)vc.stride(1), (float)scale);
+        };
+        switch (G) {   // checked above: 1, 2, 4 or 8
+            case 1: launch(std::integral_constant<int, 1>{}); break;
+            case 2: launch(std::integral_constant<int, 2>{}); break;
+            case 4: launch(std::integral_constant<int, 4>{}); break;
+            default: launch(std::integral_constant<int, 8>{}); break;
         }
-
-    switch (D) {
-        case 64: LAUNCH_RAG_D(64); break;
-        case 80: LAUNCH_RAG_D(80); break;
-        case 96: LAUNCH_RAG_D(96); break;
-        default: LAUNCH_RAG_D(128); break;
-    }
-    #undef LAUNCH_RAG_D
-    #undef LAUNCH_RAG
+    });
     HIP_CHECK_LAST();
 
     if (ns > 1) {

@@ -269,3 +269,61 @@ def test_attn_decode_matches_sdpa():
             q.float(), k.float().repeat_interleave(rep, dim=1),
             v.float().repeat_interleave(rep, dim=1))
         assert torch.allclose(out.float(), ref, atol=2e-2), (D, hkv)
+
+
+# attn_decode argument checking. Every bad tensor is the same size as or
+# LARGER than what the kernel would read, so even an unguarded launch
+# stays in bounds.
+
+def _decode_args(hkv=2):
+    B, H, S, D = 2, 4, 128, 64
+    g = torch.Generator().manual_seed(0)
+    q, k, v = (torch.randn(*shape, generator=g).to("cuda", torch.bfloat16)
+               for shape in ((B, H, 1, D), (B, hkv, S, D), (B, hkv, S, D)))
+    return [q, k, v]
+
+
+def _grown(t, dim, by):
+    shape = list(t.shape)
+    shape[dim] += by
+    return torch.zeros(shape, device=t.device, dtype=t.dtype)
+
+
+BAD_DECODE = {
+    "k_fp16": lambda a: a.__setitem__(1, a[1].to(torch.float16)),
+    "v_fp32": lambda a: a.__setitem__(2, a[2].float()),
+    "v_head_dim_plus_16": lambda a: a.__setitem__(2, _grown(a[2], 3, 16)),
+    "v_batch_plus_1": lambda a: a.__setitem__(2, _grown(a[2], 0, 1)),
+    "kv_batch_plus_1": lambda a: (a.__setitem__(1, _grown(a[1], 0, 1)),
+                                  a.__setitem__(2, _grown(a[2], 0, 1))),
+    # H = 4 is not a multiple of Hkv = 3; v matches k
+    "kv_heads_3": lambda a: (a.__setitem__(1, _grown(a[1], 1, 1)),
+                             a.__setitem__(2, _grown(a[2], 1, 1))),
+}
+
+
+@pytest.mark.parametrize("bad", sorted(BAD_DECODE))
+def test_attn_decode_rejects(ext, bad):
+    args = _decode_args()
+    BAD_DECODE[bad](args)
+    with pytest.raises(RuntimeError):
+        ext.attn_decode(*args, 0.125)
+    torch.cuda.synchronize()
+
+
+def test_attn_decode_accepts_valid_arguments(ext):
+    """The checks must not reject what decode_attention passes: contiguous
+    k/v and a transposed view of a [B, S, Hkv, D] cache give the same
+    answer, which matches SDPA as in test_attn_decode_matches_sdpa."""
+    q, k, v = _decode_args()
+    out = ext.attn_decode(q, k, v, 0.125)
+    kt = k.transpose(1, 2).contiguous().transpose(1, 2)
+    vt = v.transpose(1, 2).contiguous().transpose(1, 2)
+    assert not kt.is_contiguous() and not vt.is_contiguous()
+    out_t = ext.attn_decode(q, kt, vt, 0.125)
+    rep = q.size(1) // k.size(1)
+    ref = torch.nn.functional.scaled_dot_product_attention(
+        q.float(), k.float().repeat_interleave(rep, dim=1),
+        v.float().repeat_interleave(rep, dim=1))
+    assert torch.allclose(out.float(), ref, atol=2e-2)
+    assert torch.equal(out, out_t)
