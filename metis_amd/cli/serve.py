@@ -16,7 +16,9 @@ the default GPU decode path of per-request generate() calls;
 ``--continuous`` serves every request through one shared
 ContinuousBatcher decode loop (requests join and leave the running
 batch between steps), whose padded ragged cache is read by the split-S
-ragged kernel (decode_ragged.hip) instead.
+ragged kernel (decode_ragged.hip) instead. ``--weight-dtype fp8`` quantises
+the linear weights once at load (e4m3fn, per-channel scales) and decodes
+through the weight-only fp8 kernel (w8_linear.hip); the default stays bf16.
 """
 
 from __future__ import annotations
@@ -31,6 +33,8 @@ from metis_amd.models.llama import LlamaModel, LlamaModelSpec, LLAMA_SPECS
 MODEL_SPECS = {**_GPT_SPECS, **LLAMA_SPECS}
 from metis_amd.runtime.generate import (ContinuousBatcher, generate,  # noqa: E402
                                          generate_ragged)
+from metis_amd.runtime.quantize import (quantize_for_decode,  # noqa: E402
+                                         weight_dtype_of)
 
 
 class BatcherWorker:
@@ -89,7 +93,8 @@ class BatcherWorker:
 
 
 def load_model(model_name: str, checkpoint: str = None,
-               dtype=torch.bfloat16, device=None):
+               dtype=torch.bfloat16, device=None, weight_dtype: str = "bf16"):
+    assert weight_dtype in ("bf16", "fp8"), weight_dtype
     spec = MODEL_SPECS[model_name]
     cls = LlamaModel if isinstance(spec, LlamaModelSpec) else GPTModel
     model = cls(spec, dtype=dtype)
@@ -99,9 +104,11 @@ def load_model(model_name: str, checkpoint: str = None,
         assert plan.get("tp", 1) == 1 and plan.get("pp", 1) == 1, (
             "serve v1 loads tp=pp=1 checkpoints")
         model.load_state_dict(state["model"])
+    model.eval()
+    if weight_dtype == "fp8":   # after the checkpoint, before the move
+        quantize_for_decode(model)
     if device is not None:
         model = model.to(device)
-    model.eval()
     return model, spec
 
 
@@ -130,7 +137,8 @@ def build_app(model, spec, device=None, continuous: bool = False,
     @app.get("/health")
     def health():
         return {"status": "ok", "model": spec.name,
-                "seq_length": spec.seq_length}
+                "seq_length": spec.seq_length,
+                "weight_dtype": weight_dtype_of(model)}
 
     @app.post("/generate")
     def gen(req: GenRequest):
@@ -183,11 +191,14 @@ def main() -> None:
                    help="serve through one shared continuous-batching "
                         "decode loop")
     p.add_argument("--max-batch", type=int, default=8)
+    p.add_argument("--weight-dtype", choices=("bf16", "fp8"), default="bf16",
+                   help="fp8: weight-only e4m3fn linears, quantised at load")
     args = p.parse_args()
 
     device = "cuda:0" if torch.cuda.is_available() else None
     dtype = torch.bfloat16 if torch.cuda.is_available() else torch.float32
-    model, spec = load_model(args.model, args.checkpoint, dtype, device)
+    model, spec = load_model(args.model, args.checkpoint, dtype, device,
+                             weight_dtype=args.weight_dtype)
 
     import uvicorn
 

@@ -18,6 +18,10 @@ torch::Tensor attn_decode(
 torch::Tensor attn_decode_ragged(
     torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor kv_lens,
     double scale, long num_splits);
+torch::Tensor w8_linear(
+    torch::Tensor x, torch::Tensor w8, torch::Tensor scale,
+    c10::optional<torch::Tensor> bias, long num_splits);
+long w8_linear_auto_splits(long N, long K);
 torch::Tensor ce_row_max(torch::Tensor logits);
 torch::Tensor ce_row_sumexp(torch::Tensor logits, torch::Tensor m);
 std::vector<torch::Tensor> qkv_rope_split(
@@ -109,6 +113,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           pybind11::arg("q"), pybind11::arg("k"), pybind11::arg("v"),
           pybind11::arg("kv_lens"), pybind11::arg("scale"),
           pybind11::arg("num_splits") = 0);
+    m.def("w8_linear", &w8_linear,
+          "fp8 (e4m3fn) weight-only linear for 1 <= M <= 16 bf16 rows: "
+          "scale[n] * (x @ w8^T) + bias, fp32 accumulation, split-K",
+          pybind11::arg("x"), pybind11::arg("w8"), pybind11::arg("scale"),
+          pybind11::arg("bias") = pybind11::none(),
+          pybind11::arg("num_splits") = 0);
+    m.def("w8_linear_auto_splits", &w8_linear_auto_splits,
+          "split count w8_linear picks for num_splits = 0 (from N and K only)");
     m.def("ce_row_max", &ce_row_max, "per-row max of bf16 logits (fp32)");
     m.def("ce_row_sumexp", &ce_row_sumexp,
           "per-row sum(exp(x - m)) of bf16 logits (fp32)");

@@ -15,7 +15,23 @@ Two further modes:
   --ragged   the continuous-batching workload (llama3-1b, 8 requests,
              prompts 64-183 tokens, 32 new each, ContinuousBatcher), once
              per METIS_DECODE_KERNEL value in fresh child processes,
-             alternated; prints tok/s per repeat and the spread.
+             alternated; prints tok/s per repeat and the spread. With
+             --ab-weights the two arms are bf16 and fp8 weights instead
+             (METIS_DECODE_KERNEL left alone), and peak allocated memory
+             is reported per arm.
+  --linear   device-event timing of the fp8 weight-only decode linear
+             (w8_linear.hip) against bf16 F.linear (hipBLASLt) on the
+             llama3-1b / llama3-8b linears at M in {1, 4, 8, 16}, the two
+             alternated call by call while rotating through enough distinct
+             weight buffers that either arm's set exceeds the 256 MiB
+             last-level cache; --sweep-splits adds explicit split counts.
+
+  --steady   steady decoding, bf16 against fp8 weights in one process:
+             batch 8, a 64-token prefill into a KVCache, then 64 timed
+             single-token steps per arm, arms alternated; ms/step.
+
+--weight-dtype fp8 quantises the model (runtime.quantize) in the
+end-to-end modes.
 """
 import argparse
 import json
@@ -100,17 +116,129 @@ def kernel_mode(args):
             report(B, H, Hkv, D, S, lens, "S/8..S")
 
 
+LINEAR_SPLIT_SWEEP = (1, 2, 4, 8, 16)
+LLC_BYTES = 256 << 20
+
+
+def linear_mode(args):
+    import torch.nn.functional as F
+
+    from metis_amd.models.llama import LLAMA_SPECS
+    from metis_amd.ops import require_extension
+    from metis_amd.ops.w8 import quantize_weight_e4m3
+
+    ext = require_extension()
+    torch.manual_seed(0)
+    sweep = LINEAR_SPLIT_SWEEP if args.sweep_splits else ()
+    print("linear model      layer       N      K   M bufs splits |"
+          "    fp8 us  TB/s  %HBM |   bf16 us  TB/s  %HBM | speedup"
+          + ("".join(f" | ns={n:<2d} us" for n in sweep)), flush=True)
+    for name in ("llama3-1b", "llama3-8b"):
+        spec = LLAMA_SPECS[name]
+        h, f, d = spec.hidden_size, spec.ffn_hidden_size, spec.head_dim
+        layers = (("qkv", (spec.num_heads + 2 * spec.num_kv_heads) * d, h),
+                  ("proj", h, h), ("gate_up", 2 * f, h), ("down", h, f),
+                  ("head", spec.vocab_size, h))
+        for layer, N, K in layers:
+            # distinct buffers: the fp8 set alone exceeds the cache
+            nbuf = max(2, -(-(LLC_BYTES * 5 // 4) // (N * K)))
+            w = torch.randn(N, K, device="cuda", dtype=torch.bfloat16) * 0.02
+            w8, scale = quantize_weight_e4m3(w)
+            bias = torch.zeros(N, device="cuda", dtype=torch.bfloat16)
+            w8s = [w8.clone() for _ in range(nbuf)]
+            wbs = [w.clone() for _ in range(nbuf)]
+            del w, w8
+            ns_auto = ext.w8_linear_auto_splits(N, K)
+            for M in (1, 4, 8, 16):
+                x = torch.randn(M, K, device="cuda", dtype=torch.bfloat16)
+                # each arm starts elsewhere in the ring, so no arm finds
+                # a buffer another arm has just pulled into the cache
+                arms = 2 + len(sweep)
+                turn = [a * nbuf // arms for a in range(arms)]
+
+                def nxt(arm):
+                    turn[arm] = (turn[arm] + 1) % nbuf
+                    return turn[arm]
+
+                fns = [lambda: ext.w8_linear(x, w8s[nxt(0)], scale, bias),
+                       lambda: F.linear(x, wbs[nxt(1)], bias)]
+                for j, ns in enumerate(sweep):
+                    fns.append(lambda ns=ns, j=j: ext.w8_linear(
+                        x, w8s[nxt(2 + j)], scale, bias, ns))
+                us = _time_alternating(fns, args.iters, args.warmup)
+
+                def cols(t, nbytes):
+                    bps = nbytes / (t * 1e-6)
+                    return (f"{t:9.1f} {bps / 1e12:5.2f} "
+                            f"{100 * bps / HBM_ACHIEVABLE:5.1f}")
+
+                print(f"linear {name:10s} {layer:8s} {N:6d} {K:6d} {M:3d} "
+                      f"{nbuf:4d} {ns_auto:6d} | {cols(us[0], N * K)} | "
+                      f"{cols(us[1], 2 * N * K)} | {us[1] / us[0]:6.2f}x"
+                      + "".join(f" | {t:8.1f}" for t in us[2:]), flush=True)
+            del w8s, wbs
+            torch.cuda.empty_cache()
+
+
+def steady_mode(args):
+    """Decode steps only (no prefill in the timed window): what the fp8
+    weight-only kernel buys once a batch is running."""
+    from metis_amd.models.llama import LLAMA_SPECS
+    from metis_amd.runtime.generate import KVCache
+    from metis_amd.runtime.quantize import quantize_for_decode
+
+    spec = LLAMA_SPECS[args.model]
+    with torch.device("cuda"):
+        torch.manual_seed(0)
+        dense = LlamaModel(spec, tp=1, dtype=torch.bfloat16).eval()
+        torch.manual_seed(0)
+        quant = LlamaModel(spec, tp=1, dtype=torch.bfloat16).eval()
+    quantize_for_decode(quant)
+    torch.cuda.empty_cache()
+    B, P, steps = args.batch, 64, 64
+    toks = torch.randint(0, spec.vocab_size, (B, P), device="cuda")
+    nxt = torch.randint(0, spec.vocab_size, (B, 1), device="cuda")
+    res = {"bf16": [], "fp8": []}
+    with torch.no_grad():
+        for rep in range(args.repeats + 1):         # first round warms up
+            for label, model in (("bf16", dense), ("fp8", quant)):
+                cache = KVCache()
+                model(toks, cache=cache, pos_offset=0)
+                for i in range(4):                  # warm the step shapes
+                    model(nxt, cache=cache, pos_offset=P + i)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for i in range(steps):
+                    model(nxt, cache=cache, pos_offset=P + 4 + i)
+                torch.cuda.synchronize()
+                if rep:
+                    res[label].append(
+                        (time.perf_counter() - t0) * 1e3 / steps)
+    for label in ("bf16", "fp8"):
+        r = res[label]
+        med = statistics.median(r)
+        print(f"steady {args.model} batch {B} weights={label}: ms/step "
+              f"{[round(x, 3) for x in r]}, median {med:.3f} "
+              f"({B / med * 1e3:.0f} tok/s)", flush=True)
+
+
 def _ragged_child(args):
     """One process, one METIS_DECODE_KERNEL value (from the environment):
     warm up once, then time whole ContinuousBatcher runs."""
     from metis_amd.models.llama import LLAMA_SPECS
     from metis_amd.runtime.generate import ContinuousBatcher
 
-    spec = LLAMA_SPECS["llama3-1b"]
+    spec = LLAMA_SPECS[args.model]
     torch.manual_seed(0)
     with torch.device("cuda"):
         model = LlamaModel(spec, tp=1, dtype=torch.bfloat16)
     model.eval()
+    if args.weight_dtype == "fp8":
+        from metis_amd.runtime.quantize import quantize_for_decode
+
+        quantize_for_decode(model)
+        torch.cuda.empty_cache()
+    torch.cuda.reset_peak_memory_stats()
     g = torch.Generator().manual_seed(0)
     prompts = [torch.randint(0, spec.vocab_size, (64 + 17 * i,),
                              generator=g).tolist() for i in range(8)]
@@ -133,7 +261,44 @@ def _ragged_child(args):
     with torch.no_grad():
         run()                                   # warmup
         tps = [run() for _ in range(args.inner)]
-    print(RESULT_TAG + json.dumps({"tok_s": tps}), flush=True)
+    peak = torch.cuda.max_memory_allocated() / 2 ** 30
+    print(RESULT_TAG + json.dumps({"tok_s": tps, "peak_gib": peak}),
+          flush=True)
+
+
+def _run_child(args, env, weight_dtype):
+    out = subprocess.run(
+        [sys.executable, os.path.abspath(__file__), "--ragged-child",
+         "--inner", str(args.inner), "--model", args.model,
+         "--weight-dtype", weight_dtype],
+        env=env, check=True, capture_output=True, text=True).stdout
+    line = [ln for ln in out.splitlines() if ln.startswith(RESULT_TAG)][-1]
+    return json.loads(line[len(RESULT_TAG):])
+
+
+def ragged_weights_mode(args):
+    """Parent: never touches the GPU; one fresh child per measurement,
+    alternating bf16 and fp8 weights."""
+    results = {"bf16": [], "fp8": []}
+    peaks = {"bf16": [], "fp8": []}
+    for rep in range(args.repeats):
+        for wd in ("bf16", "fp8"):
+            res = _run_child(args, dict(os.environ), wd)
+            med = statistics.median(res["tok_s"])
+            results[wd].append(med)
+            peaks[wd].append(res["peak_gib"])
+            print(f"ragged {args.model} repeat {rep} weights={wd}: median "
+                  f"{med:.1f} tok/s of {[round(t, 1) for t in res['tok_s']]}, "
+                  f"peak {res['peak_gib']:.2f} GiB", flush=True)
+    for wd in ("bf16", "fp8"):
+        r = results[wd]
+        print(f"ragged {args.model} weights={wd}: median "
+              f"{statistics.median(r):.1f} tok/s, spread {max(r) - min(r):.1f} "
+              f"(min {min(r):.1f}, max {max(r):.1f}) over {len(r)} processes, "
+              f"peak allocated {max(peaks[wd]):.2f} GiB")
+    gain = statistics.median(results["fp8"]) / statistics.median(results["bf16"])
+    print(f"ragged {args.model} verdict: fp8 weights {100 * (gain - 1):+.1f}% "
+          f"tok/s vs bf16 (opt-in either way: fp8 changes the numerics)")
 
 
 def ragged_mode(args):
@@ -143,13 +308,7 @@ def ragged_mode(args):
     for rep in range(args.repeats):
         for flag in ("0", "1"):
             env = dict(os.environ, METIS_DECODE_KERNEL=flag)
-            out = subprocess.run(
-                [sys.executable, os.path.abspath(__file__), "--ragged-child",
-                 "--inner", str(args.inner)],
-                env=env, check=True, capture_output=True, text=True).stdout
-            line = [ln for ln in out.splitlines()
-                    if ln.startswith(RESULT_TAG)][-1]
-            tps = json.loads(line[len(RESULT_TAG):])["tok_s"]
+            tps = _run_child(args, env, args.weight_dtype)["tok_s"]
             med = statistics.median(tps)
             results[flag].append(med)
             print(f"ragged repeat {rep} METIS_DECODE_KERNEL={flag}: "
@@ -183,6 +342,17 @@ def main():
                     help="continuous-batching A/B over METIS_DECODE_KERNEL")
     ap.add_argument("--ragged-child", action="store_true",
                     help=argparse.SUPPRESS)
+    ap.add_argument("--linear", action="store_true",
+                    help="w8_linear.hip vs bf16 F.linear kernel timing")
+    ap.add_argument("--steady", action="store_true",
+                    help="decode-steps-only ms/step, bf16 vs fp8 weights")
+    ap.add_argument("--sweep-splits", action="store_true",
+                    help="--linear: also time explicit num_splits values")
+    ap.add_argument("--weight-dtype", choices=("bf16", "fp8"), default="bf16",
+                    help="fp8: weight-only quantised linears (end-to-end modes)")
+    ap.add_argument("--ab-weights", action="store_true",
+                    help="--ragged: alternate bf16 / fp8 weights instead of "
+                         "METIS_DECODE_KERNEL")
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--repeats", type=int, default=3)
@@ -192,16 +362,28 @@ def main():
     if args.kernel:
         assert args.iters >= 50, "--kernel times at least 50 iterations"
         return kernel_mode(args)
+    if args.linear:
+        assert args.iters >= 50, "--linear times at least 50 iterations"
+        return linear_mode(args)
+    if args.steady:
+        return steady_mode(args)
     if args.ragged_child:
         return _ragged_child(args)
     if args.ragged:
         assert args.repeats >= 3, "--ragged needs at least 3 repeats"
+        if args.ab_weights:
+            return ragged_weights_mode(args)
         return ragged_mode(args)
 
     spec = MODEL_SPECS[args.model]
     cls = LlamaModel if isinstance(spec, LlamaModelSpec) else GPTModel
     torch.manual_seed(0)
     model = cls(spec, tp=1, dtype=torch.bfloat16).to("cuda")
+    model.eval()
+    if args.weight_dtype == "fp8":
+        from metis_amd.runtime.quantize import quantize_for_decode
+
+        quantize_for_decode(model)
     tokens = torch.randint(0, spec.vocab_size, (args.batch, args.prompt),
                            device="cuda")
     # warmup
@@ -214,7 +396,8 @@ def main():
     tps = args.batch * args.new / dt
     flag = os.environ.get("METIS_DECODE_KERNEL", "1(default)")
     print(f"decode {args.model} b{args.batch} p{args.prompt} n{args.new} "
-          f"METIS_DECODE_KERNEL={flag}: {dt*1e3:.1f} ms, {tps:.0f} tok/s")
+          f"METIS_DECODE_KERNEL={flag} weights={args.weight_dtype}: "
+          f"{dt*1e3:.1f} ms, {tps:.0f} tok/s")
     assert out.shape == (args.batch, args.prompt + args.new)
 
 

@@ -33,6 +33,7 @@ sources = [
     os.path.join(HIP_DIR, "qkv_rope.hip"),
     os.path.join(HIP_DIR, "decode.hip"),
     os.path.join(HIP_DIR, "decode_ragged.hip"),
+    os.path.join(HIP_DIR, "w8_linear.hip"),
     os.path.join(HIP_DIR, "lt_gemm.cpp"),
 ]
 sources = [s for s in sources if os.path.exists(s)]
