@@ -45,9 +45,8 @@ from metis_amd.models.gpt import (
     LayerNorm,
     _init_linear,
 )
-from metis_amd.ops.attention import flash_attention
+from metis_amd.ops.attention import packed_flash_attention
 from metis_amd.ops.cross_entropy import cross_entropy
-from metis_amd.ops.relayout import heads_merge, qkv_split_transpose
 from metis_amd.partial_grads import mark_partial
 
 
@@ -215,10 +214,9 @@ class MoEBlock(nn.Module):
         residual = x
         y = self.ln_attn(x)
         qkv = self.qkv(y, tp_group)
-        q, k, v = qkv_split_transpose(
+        attn = packed_flash_attention(
             qkv, self.heads_per_rank, self.heads_per_rank, self.head_dim)
-        attn = flash_attention(q, k, v, causal=True)
-        x = residual + self.proj(heads_merge(attn), tp_group)
+        x = residual + self.proj(attn, tp_group)
         x = x + self._moe_mlp(self.ln_mlp(x), tp_group)
         return x
 

@@ -3,6 +3,8 @@
 Forward: online-softmax flash kernel (attention.hip), saving the row LSE.
 Backward: split dQ / dKV recompute kernels (attention_bwd.hip); GQA dK/dV
 come back per q-head and reduce over the group here (deterministic).
+packed_flash_attention runs the same kernels in their packed addressing
+mode, straight on the qkv GEMM's output and into the proj GEMM's input.
 
 Unsupported shapes (head dim outside HEAD_DIMS, S % 128 != 0, non-causal)
 fall back to PyTorch SDPA: the kernels are template-instantiated per head
@@ -83,6 +85,76 @@ def flash_attention(
     return F.scaled_dot_product_attention(
         q, k, v, is_causal=causal, scale=scale, enable_gqa=q.size(1) != k.size(1)
     )
+
+
+class _PackedFlashAttention(torch.autograd.Function):
+    """Attention on the qkv GEMM's own output layout (packed mode of
+    attention.hip / attention_bwd.hip): no split/transpose before, no heads
+    merge after, and the merged output is the one tensor both this backward
+    and the proj GEMM's backward keep."""
+
+    @staticmethod
+    def forward(ctx, qkv, nq, nkv, head_dim, scale):
+        ext = _ops.require_extension()
+        qkv = qkv.contiguous()
+        o, lse = ext.attn_fwd_packed(qkv, nq, nkv, head_dim, scale)
+        ctx.save_for_backward(qkv, o, lse)
+        ctx.dims = (nq, nkv, head_dim, scale)
+        return o
+
+    @staticmethod
+    def backward(ctx, d_o):
+        ext = _ops.require_extension()
+        qkv, o, lse = ctx.saved_tensors
+        nq, nkv, head_dim, scale = ctx.dims
+        d_o = d_o.contiguous()      # expanded (zero-stride) gradients, once
+        delta = ext.attn_bwd_delta_packed(o, d_o, nq)       # fp32 [B, H, S]
+        dqkv = ext.attn_bwd_packed(qkv, d_o, lse, delta, nq, nkv, head_dim,
+                                   scale)
+        return dqkv, None, None, None, None
+
+
+def _packed_supported(qkv: torch.Tensor, nq: int, nkv: int, head_dim: int) -> bool:
+    import os
+
+    return (
+        os.environ.get("METIS_ATTN_PACKED", "1") != "0"
+        and qkv.is_cuda
+        and qkv.dtype == torch.bfloat16
+        and qkv.dim() == 3
+        and _head_dim_supported(head_dim)
+        and qkv.size(1) > 0
+        and qkv.size(1) % 128 == 0
+        and nq == nkv
+        # a contiguous view at an odd offset: the kernels' 16-B loads need
+        # an aligned base (a non-contiguous qkv is copied, hence aligned)
+        and (not qkv.is_contiguous() or qkv.data_ptr() % 16 == 0)
+    )
+
+
+def packed_flash_attention(
+    qkv: torch.Tensor,
+    nq: int,
+    nkv: int,
+    head_dim: int,
+    scale: Optional[float] = None,
+) -> torch.Tensor:
+    """Causal attention straight on qkv [B, S, (nq + 2*nkv)*D], column blocks
+    [q heads | k heads | v heads] -> [B, S, nq*D].
+
+    On CUDA bf16 with a supported head dim, S % 128 == 0 and nq == nkv the
+    kernels address qkv in place and write the merged layout. Anything else
+    (and METIS_ATTN_PACKED=0) is the three-call composition
+    qkv_split_transpose -> flash_attention -> heads_merge, with every
+    fall-back those have."""
+    if scale is None:
+        scale = 1.0 / math.sqrt(head_dim)
+    if _packed_supported(qkv, nq, nkv, head_dim):
+        return _PackedFlashAttention.apply(qkv, nq, nkv, head_dim, scale)
+    from metis_amd.ops.relayout import heads_merge, qkv_split_transpose
+
+    q, k, v = qkv_split_transpose(qkv, nq, nkv, head_dim)
+    return heads_merge(flash_attention(q, k, v, causal=True, scale=scale))
 
 
 def _ragged_supported(q: torch.Tensor, k: torch.Tensor) -> bool:

@@ -45,13 +45,15 @@ using FwdLayout = TileLayout<D, kvblk_for<D>(), THREADS / 64 * 2, RESIDENT>;
 static_assert(FwdLayout<64>::bytes == 71680 && FwdLayout<80>::bytes == 79872
               && FwdLayout<96>::bytes == 45056 && FwdLayout<128>::bytes == 53248);
 
-template <int D>
+// PACKED (attn_tile.h BlockCoord): Q, K, V point at the q, k, v column
+// blocks of one qkv [B, S, (H + 2 Hkv) * D] and O is [B, S, H * D].
+template <int D, bool PACKED>
 __global__ __launch_bounds__(THREADS, RESIDENT) void attn_fwd_kernel(
     const bf16* __restrict__ Q,   // [B, H, S, D]
     const bf16* __restrict__ K,   // [B, Hkv, S, D]
     const bf16* __restrict__ V,   // [B, Hkv, S, D]
     bf16* __restrict__ O,         // [B, H, S, D]
-    float* __restrict__ LSE,      // [B, H, S]
+    float* __restrict__ LSE,      // [B, H, S] in both modes
     int B, int H, int Hkv, int S,
     float scale) {
     const int lane = threadIdx.x & 63;
@@ -67,8 +69,9 @@ __global__ __launch_bounds__(THREADS, RESIDENT) void attn_fwd_kernel(
     constexpr int KSLOT = Geom<D>::KSLOT;
     constexpr int VROW = L::WROW;            // P tile row length
 
-    const BlockCoord bc = block_coord<D>(S / QBLK, H, Hkv, S);
+    const BlockCoord bc = block_coord<D, PACKED>(S / QBLK, H, Hkv, S);
     const long q_base = bc.q_base;
+    const int pitch = bc.qkv_pitch;
 
     // this wave's two 16-row blocks: rb index within the 128-row block
     const int rbid[2] = {wave, 7 - wave};
@@ -88,7 +91,7 @@ __global__ __launch_bounds__(THREADS, RESIDENT) void attn_fwd_kernel(
         #pragma unroll
         for (int c = 0; c < dchunks; ++c)
             q_frag[rb][c] = frag8<D>(Q + q_base, qb + rbid[rb] * 16 + col16,
-                                     c * 32 + k8 * 8);
+                                     c * 32 + k8 * 8, pitch);
 
     float m_run[2][4], l_run[2][4];
     #pragma unroll
@@ -104,15 +107,22 @@ __global__ __launch_bounds__(THREADS, RESIDENT) void attn_fwd_kernel(
     // (coalesced reads, conflict-free vector LDS writes at row stride
     // KSLOT*16 B). V: lanes walk kv rows; that walk served a transposed V
     // image that no longer exists; it stays, as changing it would change speed.
-    TileStage<KVBLK, D, THREADS, Walk::DChunksInRow, Walk::RowsInDChunk> stage;
+    // PACKED: a tile is KVBLK runs of 2*D bytes at the qkv pitch, not one
+    // run, so both operands walk whole rows (Walk::WholeRows) off an SGPR
+    // tile base; measured against the walks above in BENCHMARKS.md.
+    constexpr Walk WK = PACKED ? Walk::WholeRows : Walk::DChunksInRow;
+    constexpr Walk WV = PACKED ? Walk::WholeRows : Walk::RowsInDChunk;
+    TileStage<KVBLK, D, THREADS, WK, WV, /*STAGE_B=*/true,
+              /*LANE_OFFS=*/PACKED> stage;
     const bf16* Kh = K + bc.kv_base;
     const bf16* Vh = V + bc.kv_base;
 
     const int kv_end = qb + QBLK;
-    stage.issue_loads(Kh, Vh, 0);
+    stage.issue_loads(Kh, Vh, 0, pitch, pitch);
     for (int kv0 = 0; kv0 < kv_end; kv0 += KVBLK) {
-        stage.write_stage(Ks, Vs, Vh, kv0);
-        if (kv0 + KVBLK < kv_end) stage.issue_loads(Kh, Vh, kv0 + KVBLK);
+        stage.write_stage(Ks, Vs, Vh, kv0, pitch);
+        if (kv0 + KVBLK < kv_end) stage.issue_loads(Kh, Vh, kv0 + KVBLK, pitch,
+                                                      pitch);
         __syncthreads();
 
         // ---- per row block: S = scale * Q K^T, online softmax, P -> LDS -
@@ -220,7 +230,7 @@ __global__ __launch_bounds__(THREADS, RESIDENT) void attn_fwd_kernel(
             const float inv_l = 1.f / l_run[rb][r];
             #pragma unroll
             for (int jd = 0; jd < djtiles; ++jd)
-                O[q_base + (long)qrow * D + jd * 16 + col16] =
+                O[bc.o_base + (long)qrow * bc.o_pitch + jd * 16 + col16] =
                     __float2bfloat16(o_acc[rb][jd][r] * inv_l);
             if (col16 == 0)
                 LSE[bc.row_base + qrow] =
@@ -243,9 +253,35 @@ std::vector<torch::Tensor> attn_fwd(
     auto stream = c10::hip::getCurrentHIPStream().stream();
     dispatch_head_dim(a.D, [&](auto d) {
         constexpr int DD = decltype(d)::value;
-        hipLaunchKernelGGL(attn_fwd_kernel<DD>, dim3(grid), dim3(THREADS),
+        hipLaunchKernelGGL((attn_fwd_kernel<DD, false>), dim3(grid), dim3(THREADS),
             FwdLayout<DD>::bytes, stream,
             bf16_ptr(qc), bf16_ptr(kc), bf16_ptr(vc), bf16_ptr(o),
+            lse.data_ptr<float>(),
+            (int)a.B, (int)a.H, (int)a.Hkv, (int)a.S, (float)scale);
+    });
+    HIP_CHECK_LAST();
+    return {o, lse};
+}
+
+// Packed mode: q, k, v are read where the qkv GEMM left them and o is written
+// where the proj GEMM reads it; no relayout copy on either side.
+std::vector<torch::Tensor> attn_fwd_packed(
+    torch::Tensor qkv, long H, long Hkv, long D, double scale) {
+    const AttnDims a = check_attn_packed_qkv(qkv, H, Hkv, D);
+
+    // every element is written by the kernel: 128-row tiles cover S, the
+    // djtiles column tiles cover D, the grid covers every (batch, head)
+    auto o = torch::empty({a.B, a.S, a.H * a.D}, qkv.options());
+    auto lse = torch::empty({a.B, a.H, a.S}, qkv.options().dtype(torch::kFloat32));
+
+    const int grid = (int)(a.B * a.H * (a.S / QBLK));
+    auto stream = c10::hip::getCurrentHIPStream().stream();
+    const bf16* base = bf16_ptr(qkv);
+    dispatch_head_dim(a.D, [&](auto d) {
+        constexpr int DD = decltype(d)::value;
+        hipLaunchKernelGGL((attn_fwd_kernel<DD, true>), dim3(grid), dim3(THREADS),
+            FwdLayout<DD>::bytes, stream,
+            base, base + a.H * a.D, base + (a.H + a.Hkv) * a.D, bf16_ptr(o),
             lse.data_ptr<float>(),
             (int)a.B, (int)a.H, (int)a.Hkv, (int)a.S, (float)scale);
     });

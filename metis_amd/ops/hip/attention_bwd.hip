@@ -60,7 +60,10 @@ static_assert(DkvLayout<64>::bytes == 55296 && DkvLayout<80>::bytes == 40960
               && DkvLayout<96>::bytes == 45056 && DkvLayout<128>::bytes == 53248);
 
 // ---------------------------------------------------------------- dQ ----
-template <int D>
+// PACKED (attn_tile.h BlockCoord) in both kernels: Q, K, V and dQ / dK, dV
+// point at the q, k, v column blocks of qkv and dqkv [B, S, (H + 2 Hkv) * D];
+// dO is [B, S, H * D]; LSE and Delta stay [B, H, S].
+template <int D, bool PACKED>
 __global__ __launch_bounds__(THREADS, RESIDENT) void attn_bwd_dq_kernel(
     const bf16* __restrict__ Q, const bf16* __restrict__ K,
     const bf16* __restrict__ V, const bf16* __restrict__ dO,
@@ -77,8 +80,9 @@ __global__ __launch_bounds__(THREADS, RESIDENT) void attn_bwd_dq_kernel(
     constexpr int djtiles = Geom<D>::djtiles;
     constexpr int KSLOT = Geom<D>::KSLOT;
 
-    const BlockCoord bc = block_coord<D>(S / RBLK, H, Hkv, S);
+    const BlockCoord bc = block_coord<D, PACKED>(S / RBLK, H, Hkv, S);
     const long q_base = bc.q_base, row_base = bc.row_base;
+    const int pitch = bc.qkv_pitch;
 
     const int rbid[2] = {wave, 7 - wave};
     const int qb = bc.tile * RBLK;
@@ -101,8 +105,10 @@ __global__ __launch_bounds__(THREADS, RESIDENT) void attn_bwd_dq_kernel(
         }
         #pragma unroll
         for (int c = 0; c < dchunks; ++c) {
-            q_frag[rb][c] = frag8<D>(Q + q_base, q0 + col16, c * 32 + k8 * 8);
-            do_frag[rb][c] = frag8<D>(dO + q_base, q0 + col16, c * 32 + k8 * 8);
+            q_frag[rb][c] = frag8<D>(Q + q_base, q0 + col16, c * 32 + k8 * 8,
+                                     pitch);
+            do_frag[rb][c] = frag8<D>(dO + bc.o_base, q0 + col16,
+                                      c * 32 + k8 * 8, bc.o_pitch);
         }
     }
 
@@ -110,17 +116,20 @@ __global__ __launch_bounds__(THREADS, RESIDENT) void attn_bwd_dq_kernel(
 
     // T14 staged K (one natural image serves the QK^T reads and the tr16
     // reads of dS K); V has no stage registers and is loaded when its
-    // natural image is written. Lanes walk kv rows for both.
-    TileStage<CTILE, D, THREADS, Walk::RowsInDChunk, Walk::RowsInDChunk,
-              /*STAGE_B=*/false> stage;
+    // natural image is written. Lanes walk kv rows for both; in PACKED
+    // mode, where a row is its own 2*D-byte run, whole rows (dKV likewise).
+    constexpr Walk WALK = PACKED ? Walk::WholeRows : Walk::RowsInDChunk;
+    TileStage<CTILE, D, THREADS, WALK, WALK, /*STAGE_B=*/false,
+              /*LANE_OFFS=*/PACKED> stage;
     const bf16* Kh = K + bc.kv_base;
     const bf16* Vh = V + bc.kv_base;
 
     const int kv_end = qb + RBLK;
-    stage.issue_loads(Kh, Vh, 0);
+    stage.issue_loads(Kh, Vh, 0, pitch, pitch);
     for (int kv0 = 0; kv0 < kv_end; kv0 += CTILE) {
-        stage.write_stage(Ks, Vs, Vh, kv0);
-        if (kv0 + CTILE < kv_end) stage.issue_loads(Kh, Vh, kv0 + CTILE);
+        stage.write_stage(Ks, Vs, Vh, kv0, pitch);
+        if (kv0 + CTILE < kv_end)
+            stage.issue_loads(Kh, Vh, kv0 + CTILE, pitch, pitch);
         __syncthreads();
 
         bool rb_active[2];
@@ -196,7 +205,7 @@ __global__ __launch_bounds__(THREADS, RESIDENT) void attn_bwd_dq_kernel(
             const long qrow = qb + rbid[rb] * 16 + k8 * 4 + r;
             #pragma unroll
             for (int jd = 0; jd < djtiles; ++jd)
-                dQ[q_base + qrow * D + jd * 16 + col16] =
+                dQ[q_base + qrow * pitch + jd * 16 + col16] =
                     __float2bfloat16(dq_acc[rb][jd][r]);
         }
 }
@@ -209,7 +218,7 @@ __global__ __launch_bounds__(THREADS, RESIDENT) void attn_bwd_dq_kernel(
 // same change was -8.5% and at D=128/S=4096 -9.5% (deeper per-wave
 // VGPR footprints lose the second independent block's latency
 // cover), so those stay 4-wave x 64 rows.
-template <int D>
+template <int D, bool PACKED>
 __global__ __launch_bounds__(dkv_rows<D>() / 16 * 64, RESIDENT)
 void attn_bwd_dkv_kernel(
     const bf16* __restrict__ Q, const bf16* __restrict__ K,
@@ -230,9 +239,10 @@ void attn_bwd_dkv_kernel(
     constexpr int KVB = dkv_rows<D>();
     constexpr int NW = KVB / 16;             // waves per block
 
-    const BlockCoord bc = block_coord<D>(S / KVB, H, Hkv, S);
+    const BlockCoord bc = block_coord<D, PACKED>(S / KVB, H, Hkv, S);
     const long kv_base = bc.kv_base, row_base = bc.row_base;
     const long out_base = bc.q_base;      // dK/dV come back per q-head
+    const int pitch = bc.qkv_pitch;
 
     const int kv0 = bc.tile * KVB + wave * 16;   // this wave's kv rows
 
@@ -247,8 +257,8 @@ void attn_bwd_dkv_kernel(
     bf16x8 k_frag[dchunks], v_frag[dchunks];
     #pragma unroll
     for (int c = 0; c < dchunks; ++c) {
-        k_frag[c] = frag8<D>(K + kv_base, kv0 + col16, c * 32 + k8 * 8);
-        v_frag[c] = frag8<D>(V + kv_base, kv0 + col16, c * 32 + k8 * 8);
+        k_frag[c] = frag8<D>(K + kv_base, kv0 + col16, c * 32 + k8 * 8, pitch);
+        v_frag[c] = frag8<D>(V + kv_base, kv0 + col16, c * 32 + k8 * 8, pitch);
     }
 
     floatx4 dk_acc[djtiles] = {}, dv_acc[djtiles] = {};
@@ -257,16 +267,18 @@ void attn_bwd_dkv_kernel(
     // D=128 the dO set would spill past 256 VGPRs on top of the dK+dV
     // accumulators, so dO is loaded at write time there.
     constexpr bool STAGE_DO = (D <= 96);
-    TileStage<CTILE, D, NW * 64, Walk::RowsInDChunk, Walk::RowsInDChunk,
-              STAGE_DO> stage;
+    constexpr Walk WALK = PACKED ? Walk::WholeRows : Walk::RowsInDChunk;
+    TileStage<CTILE, D, NW * 64, WALK, WALK, STAGE_DO,
+              /*LANE_OFFS=*/PACKED> stage;
     const bf16* Qh = Q + bc.q_base;
-    const bf16* dOh = dO + bc.q_base;
+    const bf16* dOh = dO + bc.o_base;
 
     const int q_start = bc.tile * KVB;   // causal: from the block's kv start
-    stage.issue_loads(Qh, dOh, q_start);
+    stage.issue_loads(Qh, dOh, q_start, pitch, bc.o_pitch);
     for (int q0 = q_start; q0 < S; q0 += CTILE) {
-        stage.write_stage(Qs, dOs, dOh, q0);
-        if (q0 + CTILE < S) stage.issue_loads(Qh, dOh, q0 + CTILE);
+        stage.write_stage(Qs, dOs, dOh, q0, bc.o_pitch);
+        if (q0 + CTILE < S)
+            stage.issue_loads(Qh, dOh, q0 + CTILE, pitch, bc.o_pitch);
         __syncthreads();
 
         const bool active = q0 + CTILE - 1 >= kv0;
@@ -338,9 +350,9 @@ void attn_bwd_dkv_kernel(
         const long kvrow = kv0 + k8 * 4 + r;
         #pragma unroll
         for (int jd = 0; jd < djtiles; ++jd) {
-            dK[out_base + kvrow * D + jd * 16 + col16] =
+            dK[out_base + kvrow * pitch + jd * 16 + col16] =
                 __float2bfloat16(dk_acc[jd][r]);
-            dV[out_base + kvrow * D + jd * 16 + col16] =
+            dV[out_base + kvrow * pitch + jd * 16 + col16] =
                 __float2bfloat16(dv_acc[jd][r]);
         }
     }
@@ -350,15 +362,19 @@ void attn_bwd_dkv_kernel(
 // row term both kernels above consume. 16 lanes per row, one bf16x8 chunk
 // each (D/8 = 8/10/12/16 of them live), 4 rows per wave step, DELTA_U steps
 // in flight per thread; o and dO are read once, 4 B per row written.
+// PACKED: o and dO are [B, S, H * D], so the rows walked are in (b, s, h)
+// order and row (b, s, h) is stored to the [B, H, S] index (b * H + h) * S + s.
 constexpr int DELTA_THREADS = 256;
 constexpr int DELTA_U = 4;
 
+template <bool PACKED>
 __global__ void __launch_bounds__(DELTA_THREADS) attn_bwd_delta_kernel(
     const bf16x8* __restrict__ o,
     const bf16x8* __restrict__ d_o,
     float* __restrict__ delta,
     long rows,
-    int dv) {                       // D / 8 chunks per row, <= 16
+    int dv,                         // D / 8 chunks per row, <= 16
+    int H, int S) {                 // read in packed mode only
     const int sub = threadIdx.x & 15;
     const bool live = sub < dv;
     const int ci = live ? sub : dv - 1;     // idle lanes re-read a valid chunk
@@ -383,7 +399,15 @@ __global__ void __launch_bounds__(DELTA_THREADS) attn_bwd_delta_kernel(
         #pragma unroll
         for (int off = 8; off > 0; off >>= 1) s += __shfl_xor(s, off, WAVE_SIZE);
         const long row = row0 + u * (DELTA_THREADS / 16);
-        if (sub == 0 && row < rows) delta[row] = s;
+        if (sub == 0 && row < rows) {
+            if constexpr (PACKED) {
+                // the launcher pins rows = B * S * H below 2^31
+                const int bs = (int)row / H, h = (int)row % H;
+                delta[((long)(bs / S) * H + h) * S + bs % S] = s;
+            } else {
+                delta[row] = s;
+            }
+        }
     }
 }
 
@@ -405,11 +429,32 @@ torch::Tensor attn_bwd_delta(torch::Tensor o, torch::Tensor d_o) {
     if (rows == 0) return delta;
     const long rows_per_block = DELTA_THREADS / 16 * DELTA_U;
     const long grid = (rows + rows_per_block - 1) / rows_per_block;
-    hipLaunchKernelGGL(attn_bwd_delta_kernel, dim3((unsigned)grid),
+    hipLaunchKernelGGL(attn_bwd_delta_kernel<false>, dim3((unsigned)grid),
         dim3(DELTA_THREADS), 0, c10::hip::getCurrentHIPStream().stream(),
         reinterpret_cast<const bf16x8*>(o.data_ptr()),
         reinterpret_cast<const bf16x8*>(d_o.data_ptr()),
-        delta.data_ptr<float>(), rows, (int)(D / 8));
+        delta.data_ptr<float>(), rows, (int)(D / 8), 0, 0);
+    HIP_CHECK_LAST();
+    return delta;
+}
+
+torch::Tensor attn_bwd_delta_packed(torch::Tensor o, torch::Tensor d_o, long H) {
+    check_attn_packed_operand(o, "o");
+    TORCH_CHECK(H > 0 && o.size(2) % H == 0, "o width must be H * D");
+    const long B = o.size(0), S = o.size(1), D = o.size(2) / H;
+    check_head_dim(D);
+    check_attn_packed_out(d_o, "d_o", o, B, S, H, D);
+    TORCH_CHECK(B > 0 && S > 0 && B * H * S < (1L << 31),
+                "o must be non-empty and B * H * S must fit an int");
+    const long rows = B * S * H;
+    auto delta = torch::empty({B, H, S}, o.options().dtype(torch::kFloat32));
+    const long rows_per_block = DELTA_THREADS / 16 * DELTA_U;
+    const long grid = (rows + rows_per_block - 1) / rows_per_block;
+    hipLaunchKernelGGL(attn_bwd_delta_kernel<true>, dim3((unsigned)grid),
+        dim3(DELTA_THREADS), 0, c10::hip::getCurrentHIPStream().stream(),
+        reinterpret_cast<const bf16x8*>(o.data_ptr()),
+        reinterpret_cast<const bf16x8*>(d_o.data_ptr()),
+        delta.data_ptr<float>(), rows, (int)(D / 8), (int)H, (int)S);
     HIP_CHECK_LAST();
     return delta;
 }
@@ -443,7 +488,7 @@ std::vector<torch::Tensor> attn_bwd(
     dispatch_head_dim(a.D, [&](auto d) {
         constexpr int DD = decltype(d)::value;
         const int grid_dq = (int)(a.B * a.H * (a.S / RBLK));
-        hipLaunchKernelGGL(attn_bwd_dq_kernel<DD>, dim3(grid_dq),
+        hipLaunchKernelGGL((attn_bwd_dq_kernel<DD, false>), dim3(grid_dq),
             dim3(THREADS), DqLayout<DD>::bytes, stream,
             bf16_ptr(qc), bf16_ptr(kc), bf16_ptr(vc), bf16_ptr(doc),
             lsec.data_ptr<float>(), dc.data_ptr<float>(), bf16_ptr(dq),
@@ -451,7 +496,7 @@ std::vector<torch::Tensor> attn_bwd(
         // one block per dkv_rows kv rows, one wave per 16 of them
         constexpr int KVB = dkv_rows<DD>();
         const int grid_dkv = (int)(a.B * a.H * (a.S / KVB));
-        hipLaunchKernelGGL(attn_bwd_dkv_kernel<DD>, dim3(grid_dkv),
+        hipLaunchKernelGGL((attn_bwd_dkv_kernel<DD, false>), dim3(grid_dkv),
             dim3(KVB / 16 * 64), DkvLayout<DD>::bytes, stream,
             bf16_ptr(qc), bf16_ptr(kc), bf16_ptr(vc), bf16_ptr(doc),
             lsec.data_ptr<float>(), dc.data_ptr<float>(),
@@ -460,4 +505,44 @@ std::vector<torch::Tensor> attn_bwd(
     });
     HIP_CHECK_LAST();
     return {dq, dk, dv};
+}
+
+// Packed mode: dQ, dK, dV go straight into the q, k, v column blocks of one
+// dqkv [B, S, (H + 2 Hkv) * D], which is what the qkv GEMM's backward reads.
+torch::Tensor attn_bwd_packed(
+    torch::Tensor qkv, torch::Tensor d_o, torch::Tensor lse, torch::Tensor delta,
+    long H, long Hkv, long D, double scale) {
+    const AttnDims a = check_attn_packed_qkv(qkv, H, Hkv, D);
+    check_attn_packed_out(d_o, "d_o", qkv, a.B, a.S, a.H, a.D);
+    check_attn_rows(lse, "lse", qkv, a.B, a.H, a.S);
+    check_attn_rows(delta, "delta", qkv, a.B, a.H, a.S);
+
+    // every element is written: the dQ grid covers every (batch, head, 128
+    // q rows) of the q block, the dKV grid every (batch, head, KVB kv rows)
+    // of the k and v blocks (H == Hkv), each over all D columns
+    auto dqkv = torch::empty_like(qkv);
+
+    auto stream = c10::hip::getCurrentHIPStream().stream();
+    const bf16* in = bf16_ptr(qkv);
+    bf16* out = bf16_ptr(dqkv);
+    const long k_off = a.H * a.D, v_off = (a.H + a.Hkv) * a.D;
+    dispatch_head_dim(a.D, [&](auto d) {
+        constexpr int DD = decltype(d)::value;
+        const int grid_dq = (int)(a.B * a.H * (a.S / RBLK));
+        hipLaunchKernelGGL((attn_bwd_dq_kernel<DD, true>), dim3(grid_dq),
+            dim3(THREADS), DqLayout<DD>::bytes, stream,
+            in, in + k_off, in + v_off, bf16_ptr(d_o),
+            lse.data_ptr<float>(), delta.data_ptr<float>(), out,
+            (int)a.B, (int)a.H, (int)a.Hkv, (int)a.S, (float)scale);
+        constexpr int KVB = dkv_rows<DD>();
+        const int grid_dkv = (int)(a.B * a.H * (a.S / KVB));
+        hipLaunchKernelGGL((attn_bwd_dkv_kernel<DD, true>), dim3(grid_dkv),
+            dim3(KVB / 16 * 64), DkvLayout<DD>::bytes, stream,
+            in, in + k_off, in + v_off, bf16_ptr(d_o),
+            lse.data_ptr<float>(), delta.data_ptr<float>(),
+            out + k_off, out + v_off,
+            (int)a.B, (int)a.H, (int)a.Hkv, (int)a.S, (float)scale);
+    });
+    HIP_CHECK_LAST();
+    return dqkv;
 }

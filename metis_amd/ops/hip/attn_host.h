@@ -48,6 +48,62 @@ inline void check_head_dim(long D) {
                 "head dim must be 64/80/96/128, got ", D);
 }
 
+// One operand of the packed attention entry points: a contiguous bf16
+// [B, S, width] on the GPU whose base the kernels' 16-B loads can take.
+inline void check_attn_packed_operand(const torch::Tensor& t, const char* name) {
+    TORCH_CHECK(t.is_cuda() && t.dtype() == torch::kBFloat16,
+                name, " must be CUDA bf16");
+    TORCH_CHECK(t.dim() == 3, name, " must be [B, S, heads * D]");
+    TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0,
+                name, " must be 16-byte aligned");
+}
+
+// Packed mode: qkv [B, S, (H + 2 Hkv) * D], column blocks
+// [q heads | k heads | v heads] as qkv_split_transpose defines them. The
+// kernels address rows at a pitch of the full width, so the width, S and D
+// are pinned here; H == Hkv only (GQA keeps the [B, H, S, D] path, whose
+// per-q-head dK/dV the wrapper reduces).
+inline AttnDims check_attn_packed_qkv(const torch::Tensor& qkv, long H, long Hkv,
+                                      long D) {
+    check_attn_packed_operand(qkv, "qkv");
+    check_head_dim(D);
+    TORCH_CHECK(H > 0 && H == Hkv,
+                "packed attention needs H == Hkv > 0, got H=", H, " Hkv=", Hkv);
+    TORCH_CHECK(qkv.size(2) == (H + 2 * Hkv) * D,
+                "qkv width must be (H + 2 * Hkv) * D");
+    const AttnDims d{qkv.size(0), H, Hkv, qkv.size(1), D};
+    TORCH_CHECK(d.B > 0 && d.S > 0 && d.S % ATTN_SEQ_TILE == 0,
+                "sequence length must be a positive multiple of 128");
+    // the kernels keep 128 * pitch in an int (attn_tile.h TileStage)
+    TORCH_CHECK(d.B * d.H * d.S < (1L << 31) && qkv.size(2) < (1L << 24),
+                "B * H * S must fit an int and the row pitch be below 2^24");
+    return d;
+}
+
+// o or d_o of the packed mode: [B, S, H * D] on `like`'s device.
+inline void check_attn_packed_out(const torch::Tensor& t, const char* name,
+                                  const torch::Tensor& like, long B, long S,
+                                  long H, long D) {
+    check_attn_packed_operand(t, name);
+    TORCH_CHECK(t.get_device() == like.get_device(),
+                name, " must be on the same device as the other arguments");
+    TORCH_CHECK(t.size(0) == B && t.size(1) == S && t.size(2) == H * D,
+                name, " must be [B, S, H * D]");
+}
+
+// lse or delta: fp32 [B, H, S], contiguous, on `like`'s device.
+inline void check_attn_rows(const torch::Tensor& t, const char* name,
+                            const torch::Tensor& like, long B, long H, long S) {
+    TORCH_CHECK(t.is_cuda() && t.dtype() == torch::kFloat32,
+                name, " must be CUDA fp32");
+    TORCH_CHECK(t.get_device() == like.get_device(),
+                name, " must be on the same device as the other arguments");
+    TORCH_CHECK(t.dim() == 3 && t.size(0) == B && t.size(1) == H
+                && t.size(2) == S && t.is_contiguous(),
+                name, " must be a contiguous [B, H, S]");
+}
+
 // f(std::integral_constant<int, N>{}) with N = D.
 template <class F>
 void dispatch_head_dim(long D, F&& f) {

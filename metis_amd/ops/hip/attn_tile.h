@@ -42,12 +42,14 @@ struct TileLayout {
     static_assert(bytes * RESIDENT <= LDS_PER_CU, "resident blocks must fit one CU");
 };
 
-// A/B fragment (8 bf16 of row `row` at column d0) straight from global;
-// zero where a 32-wide chunk runs past D (D = 80).
+// A/B fragment (8 bf16 of row `row` at column d0) straight from global,
+// rows `pitch` elements apart; zero where a 32-wide chunk runs past D
+// (D = 80).
 template <int D>
-__device__ __forceinline__ bf16x8 frag8(const bf16* base, long row, int d0) {
+__device__ __forceinline__ bf16x8 frag8(const bf16* base, long row, int d0,
+                                        int pitch) {
     if (d0 < D)
-        return *reinterpret_cast<const bf16x8*>(base + row * D + d0);
+        return *reinterpret_cast<const bf16x8*>(base + row * pitch + d0);
     return bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
 }
 
@@ -93,30 +95,55 @@ __device__ __forceinline__ bf16x8 tr16_frag(
     return out;
 }
 
-// blockIdx.x = (batch * H + head) * tiles + tile: the tile index and the
-// offsets of that q head and of its GQA kv head.
+// blockIdx.x = (batch * H + head) * tiles + tile: the tile index, the
+// offsets of row 0 of that q head and of its GQA kv head, and the distance
+// between consecutive rows of one head (wave-uniform: SGPRs).
+//
+// Two addressing modes. Unpacked: q/o/dO/dQ are [B, H, S, D] and k/v
+// [B, Hkv, S, D], every pitch is the constant D. PACKED (H == Hkv only):
+// q, k, v (and dq, dk, dv) are the three column blocks of ONE
+// [B, S, (H + 2 Hkv) * D] buffer, the k and v pointers already advanced to
+// their block's first column by the launcher, so one base serves all three;
+// o and dO are [B, S, H * D]. LSE / delta rows are [B, H, S] in both.
 struct BlockCoord {
     int tile;
-    long q_base, kv_base;   // element offsets into [B, H|Hkv, S, D]
+    long q_base, kv_base;   // row 0 of the head in q|dq and in k|v|dk|dv
+    long o_base;            // row 0 of the head in o|dO
     long row_base;          // row offset into [B, H, S]
+    int qkv_pitch;          // elements between rows of q, k, v, dq, dk, dv
+    int o_pitch;            // elements between rows of o, dO
 };
 
-template <int D>
+template <int D, bool PACKED>
 __device__ __forceinline__ BlockCoord block_coord(int tiles, int H, int Hkv, int S) {
     const int head = (blockIdx.x / tiles) % H;
     const int batch = blockIdx.x / tiles / H;
-    const int kv_head = head / (H / Hkv);
     BlockCoord c;
     c.tile = blockIdx.x % tiles;
     c.row_base = ((long)batch * H + head) * S;
-    c.q_base = c.row_base * D;
-    c.kv_base = (((long)batch * Hkv + kv_head) * S) * D;
+    if constexpr (PACKED) {
+        const int HT = H + 2 * Hkv;
+        c.qkv_pitch = HT * D;
+        c.o_pitch = H * D;
+        c.q_base = c.kv_base = ((long)batch * S * HT + head) * D;
+        c.o_base = ((long)batch * S * H + head) * D;
+    } else {
+        const int kv_head = head / (H / Hkv);
+        c.qkv_pitch = c.o_pitch = D;
+        c.q_base = c.o_base = c.row_base * D;
+        c.kv_base = (((long)batch * Hkv + kv_head) * S) * D;
+    }
     return c;
 }
 
-// How consecutive 16-B chunk indices (= consecutive lanes) walk a
-// [ROWS][D] tile: along a row first, or down the rows of one d-chunk.
-enum class Walk { DChunksInRow, RowsInDChunk };
+// How the NT threads of a block walk the 16-B chunks of a [ROWS][D] tile.
+// The first two number the chunks c = thread + u * NT and lay consecutive c
+// along a row first, or down the rows of one d-chunk. WholeRows gives each
+// pass u the next NT / (D/8) whole rows, thread t taking chunk t % (D/8) of
+// row t / (D/8) (threads past the last whole row idle): the same lanes-along-
+// a-row order as DChunksInRow, but a thread's chunks are a constant number of
+// rows apart whatever D/8 is, so one lane offset serves every pass.
+enum class Walk { DChunksInRow, RowsInDChunk, WholeRows };
 
 template <int ROWS, int D, Walk W>
 __device__ __forceinline__ void chunk_pos(int c, int& row, int& d0) {
@@ -133,49 +160,84 @@ __device__ __forceinline__ void chunk_pos(int c, int& row, int& d0) {
 // natural LDS images by NT threads: issue_loads() one tile AHEAD (HBM
 // latency hides under the current tile's compute), write_stage() at loop
 // top. With STAGE_B false B has no registers and is loaded at write time.
-template <int ROWS, int D, int NT, Walk WA, Walk WB, bool STAGE_B = true>
+// LANE_OFFS splits each address into a wave-uniform 64-bit base (the first
+// row of the tile, or of the pass) and a loop-invariant unsigned 32-bit lane
+// offset in bytes, the form the load takes an SGPR base for; (row * pitch +
+// d0) * 2 < 2^32 because the packed launchers pin the pitch below 2^24.
+template <int ROWS, int D, int NT, Walk WA, Walk WB, bool STAGE_B = true,
+          bool LANE_OFFS = false>
 struct TileStage {
+    static_assert((WA == Walk::WholeRows) == (WB == Walk::WholeRows));
+    static constexpr bool whole_rows = WA == Walk::WholeRows;
     static constexpr int chunks = ROWS * D / 8;     // 16-B chunks per tile
-    static constexpr int per_thread = (chunks + NT - 1) / NT;
+    static constexpr int pass_rows = NT / (D / 8);  // WholeRows: rows per pass
+    static constexpr int per_thread =
+        whole_rows ? (ROWS + pass_rows - 1) / pass_rows : (chunks + NT - 1) / NT;
 
     bf16x8 a[per_thread];
     bf16x8 b[STAGE_B ? per_thread : 1];
 
+    // Position of this thread's chunk of pass u: row = urow (wave-uniform) +
+    // lrow, column d0; false once the thread has no chunk left.
     template <Walk W>
-    static __device__ __forceinline__ bf16x8 load(const bf16* src, int row0, int c) {
-        int row, d0;
-        chunk_pos<ROWS, D, W>(c, row, d0);
-        return *reinterpret_cast<const bf16x8*>(src + (long)(row0 + row) * D + d0);
-    }
-    template <Walk W>
-    static __device__ __forceinline__ void store(short* img, int c, bf16x8 val) {
-        int row, d0;
-        chunk_pos<ROWS, D, W>(c, row, d0);
-        *reinterpret_cast<bf16x8*>(img + Geom<D>::tile(row) + d0) = val;
+    static __device__ __forceinline__ bool pos(int u, int& urow, int& lrow, int& d0) {
+        if constexpr (W == Walk::WholeRows) {
+            urow = u * pass_rows;
+            lrow = threadIdx.x / (D / 8);
+            d0 = threadIdx.x % (D / 8) * 8;
+            return lrow < pass_rows && urow + lrow < ROWS;
+        } else {
+            const int c = threadIdx.x + u * NT;
+            urow = 0;
+            chunk_pos<ROWS, D, W>(c, lrow, d0);
+            return c < chunks;
+        }
     }
 
-    // A and B point at row 0 of this head; row0 is the tile's first row
+    template <Walk W>
+    static __device__ __forceinline__ bf16x8 load(const bf16* src, int row0, int u,
+                                                  int pitch) {
+        int urow, lrow, d0;
+        pos<W>(u, urow, lrow, d0);
+        if constexpr (LANE_OFFS) {
+            const unsigned lane_off = (unsigned)(lrow * pitch + d0) * 2u;
+            return *reinterpret_cast<const bf16x8*>(
+                reinterpret_cast<const char*>(src + (long)(row0 + urow) * pitch)
+                + lane_off);
+        }
+        return *reinterpret_cast<const bf16x8*>(
+            src + (long)(row0 + urow + lrow) * pitch + d0);
+    }
+    template <Walk W>
+    static __device__ __forceinline__ void store(short* img, int u, bf16x8 val) {
+        int urow, lrow, d0;
+        pos<W>(u, urow, lrow, d0);
+        *reinterpret_cast<bf16x8*>(img + Geom<D>::tile(urow + lrow) + d0) = val;
+    }
+
+    // A and B point at row 0 of this head, their rows pitch_a and pitch_b
+    // elements apart; row0 is the tile's first row
     __device__ __forceinline__ void issue_loads(
-        const bf16* A, const bf16* B, int row0) {
+        const bf16* A, const bf16* B, int row0, int pitch_a, int pitch_b) {
         #pragma unroll
         for (int u = 0; u < per_thread; ++u) {
-            const int c = threadIdx.x + u * NT;
-            if (c >= chunks) break;
-            a[u] = load<WA>(A, row0, c);
-            if constexpr (STAGE_B) b[u] = load<WB>(B, row0, c);
+            int urow, lrow, d0;
+            if (!pos<WA>(u, urow, lrow, d0)) break;
+            a[u] = load<WA>(A, row0, u, pitch_a);
+            if constexpr (STAGE_B) b[u] = load<WB>(B, row0, u, pitch_b);
         }
     }
     __device__ __forceinline__ void write_stage(
-        short* As, short* Bs, const bf16* B, int row0) {
+        short* As, short* Bs, const bf16* B, int row0, int pitch_b) {
         #pragma unroll
         for (int u = 0; u < per_thread; ++u) {
-            const int c = threadIdx.x + u * NT;
-            if (c >= chunks) break;
-            store<WA>(As, c, a[u]);
+            int urow, lrow, d0;
+            if (!pos<WA>(u, urow, lrow, d0)) break;
+            store<WA>(As, u, a[u]);
             bf16x8 bv;
             if constexpr (STAGE_B) bv = b[u];
-            else bv = load<WB>(B, row0, c);
-            store<WB>(Bs, c, bv);
+            else bv = load<WB>(B, row0, u, pitch_b);
+            store<WB>(Bs, u, bv);
         }
     }
 };

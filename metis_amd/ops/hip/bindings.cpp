@@ -44,6 +44,12 @@ std::vector<torch::Tensor> attn_bwd(
     torch::Tensor d_o, torch::Tensor lse, torch::Tensor delta,
     double scale);
 torch::Tensor attn_bwd_delta(torch::Tensor o, torch::Tensor d_o);
+std::vector<torch::Tensor> attn_fwd_packed(
+    torch::Tensor qkv, long H, long Hkv, long D, double scale);
+torch::Tensor attn_bwd_delta_packed(torch::Tensor o, torch::Tensor d_o, long H);
+torch::Tensor attn_bwd_packed(
+    torch::Tensor qkv, torch::Tensor d_o, torch::Tensor lse, torch::Tensor delta,
+    long H, long Hkv, long D, double scale);
 torch::Tensor gemm_bf16(
     torch::Tensor a, torch::Tensor b_nk, c10::optional<torch::Tensor> bias,
     long epilogue);
@@ -83,6 +89,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "flash attention backward -> (dQ, dK_per_head, dV_per_head)");
     m.def("attn_bwd_delta", &attn_bwd_delta,
           "rowsum(dO * O) in fp32 -> [B,H,S] (contiguous bf16 inputs)");
+    m.def("attn_fwd_packed", &attn_fwd_packed,
+          "flash attention forward on qkv [B,S,(H+2Hkv)D] in place "
+          "(H == Hkv) -> (O [B,S,H*D], LSE [B,H,S])");
+    m.def("attn_bwd_delta_packed", &attn_bwd_delta_packed,
+          "rowsum(dO * O) of [B,S,H*D] operands in fp32 -> [B,H,S]");
+    m.def("attn_bwd_packed", &attn_bwd_packed,
+          "flash attention backward on qkv in place -> dqkv [B,S,(H+2Hkv)D]");
     m.def("gemm_bf16", &gemm_bf16,
           "MFMA bf16 GEMM A[M,K] @ B[N,K]^T with fused epilogue "
           "(0=none, 1=bias, 2=bias+gelu)");
