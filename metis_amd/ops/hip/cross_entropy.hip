@@ -56,12 +56,18 @@ __global__ void ce_fwd_kernel(
         sum = block_reduce_sum(sum, scratch);
 
         if (threadIdx.x == 0) {
+            // a label outside [0, V) is never dereferenced: lse is written
+            // as usual and the row's loss is NaN (loud, no device sync)
             const long tgt = labels[row];
-            const float tl = bf16_bits_to_float(
-                reinterpret_cast<const short*>(lrow)[tgt]);
-            const float l = m + __logf(sum);
-            lse[row] = l;
-            loss[row] = l - tl;
+            float tl = __builtin_nanf("");
+            if (tgt >= 0 && tgt < (long)vv * VEC)
+                tl = bf16_bits_to_float(
+                    reinterpret_cast<const short*>(lrow)[tgt]);
+            const float ls = __logf(sum);
+            lse[row] = m + ls;
+            // (m - tl) + log(sum), not lse - tl: m - tl is exact, so a
+            // large common offset of the row costs the loss nothing
+            loss[row] = (m - tl) + ls;
         }
         __syncthreads();
     }
@@ -184,9 +190,10 @@ std::vector<torch::Tensor> cross_entropy_fwd(
     TORCH_CHECK(logits.is_cuda() && logits.dtype() == torch::kBFloat16);
     TORCH_CHECK(logits.dim() == 2 && logits.size(1) % 8 == 0,
                 "logits must be [N, V] with V % 8 == 0");
-    TORCH_CHECK(labels.dtype() == torch::kInt64);
-    auto lc = logits.contiguous();
     const long N = logits.size(0), V = logits.size(1);
+    TORCH_CHECK(labels.is_cuda() && labels.dtype() == torch::kInt64
+                && labels.numel() == N, "labels must be CUDA int64 [N]");
+    auto lc = logits.contiguous();
 
     auto f32 = logits.options().dtype(torch::kFloat32);
     auto loss = torch::empty({N}, f32);
@@ -205,8 +212,20 @@ std::vector<torch::Tensor> cross_entropy_fwd(
 torch::Tensor cross_entropy_bwd(
     torch::Tensor logits, torch::Tensor labels, torch::Tensor lse,
     torch::Tensor grad_scale) {
-    auto lc = logits.contiguous();
+    TORCH_CHECK(logits.is_cuda() && logits.dtype() == torch::kBFloat16,
+                "logits must be CUDA bf16");
+    TORCH_CHECK(logits.dim() == 2 && logits.size(1) % 8 == 0,
+                "logits must be [N, V] with V % 8 == 0");
     const long N = logits.size(0), V = logits.size(1);
+    TORCH_CHECK(labels.is_cuda() && labels.dtype() == torch::kInt64
+                && labels.numel() == N, "labels must be CUDA int64 [N]");
+    TORCH_CHECK(lse.is_cuda() && lse.dtype() == torch::kFloat32
+                && lse.numel() == N && lse.is_contiguous(),
+                "lse must be contiguous CUDA fp32 [N]");
+    TORCH_CHECK(grad_scale.is_cuda() && grad_scale.dtype() == torch::kFloat32
+                && grad_scale.numel() == 1,
+                "grad_scale must be a CUDA fp32 scalar tensor");
+    auto lc = logits.contiguous();
     auto dlogits = torch::empty_like(lc);
     const int grid = (int)std::min<long>(N, 2048);
     hipLaunchKernelGGL(ce_bwd_kernel, dim3(grid), dim3(BLOCK), 0,

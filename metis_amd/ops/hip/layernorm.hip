@@ -20,6 +20,7 @@ namespace {
 
 constexpr int BLOCK = 256;
 constexpr int VEC = 8;   // bf16 per lane per step (16 B)
+static_assert(BLOCK / WAVE_SIZE == 4, "ln_fwd_kernel adds four wave totals");
 
 __global__ void ln_fwd_kernel(
     const bf16x8* __restrict__ x,
@@ -31,28 +32,70 @@ __global__ void ln_fwd_kernel(
     int rows,
     int hv,            // H / VEC
     float eps) {
-    __shared__ float scratch[BLOCK / WAVE_SIZE];
+    __shared__ float scratch[3][BLOCK / WAVE_SIZE];
+    const int lane = threadIdx.x & (WAVE_SIZE - 1);
+    const int wave = threadIdx.x / WAVE_SIZE;
 
     for (int row = blockIdx.x; row < rows; row += gridDim.x) {
         const bf16x8* xrow = x + (long)row * hv;
 
-        float sum = 0.f, sumsq = 0.f;
+        // One statistics pass, three sums. The mean comes from the plain
+        // sum. The variance comes from shifted sums: with d = x - K,
+        // var = E[d^2] - E[d]^2 subtracts numbers of the size of the
+        // variance, where E[x^2] - mean^2 subtracts two of the size of the
+        // squared mean and loses (mean/std)^2 ulps. K is the mean of the
+        // row's first 8 elements (one 16-byte load, the same for every
+        // thread) rounded to the bf16 grid of the largest of them: d then
+        // has as few bits as x, and the sums of d*d stay as nearly exact
+        // as sums of squares of bf16 numbers are.
+        float shift = 0.f;
+        {
+            const bf16x8 v0 = xrow[0];
+            float amax = 0.f;
+            #pragma unroll
+            for (int k = 0; k < VEC; ++k) {
+                const float f = bf16_bits_to_float(v0[k]);
+                shift += f;
+                amax = fmaxf(amax, fabsf(f));
+            }
+            shift *= 1.f / VEC;
+            // 1.5 * 2^23 grid units: adding and subtracting it rounds to
+            // the grid (2^-7 of amax's power of two)
+            const float big = __uint_as_float(
+                __float_as_uint(amax) & 0x7f800000u) * 98304.f;
+            shift = (shift + big) - big;
+        }
+        float sum = 0.f, dsum = 0.f, dsumsq = 0.f;
         for (int i = threadIdx.x; i < hv; i += BLOCK) {
             bf16x8 v = xrow[i];
             #pragma unroll
             for (int k = 0; k < VEC; ++k) {
                 float f = bf16_bits_to_float(v[k]);
+                float d = f - shift;
                 sum += f;
-                sumsq += f * f;
+                dsum += d;
+                dsumsq += d * d;
             }
         }
-        sum = block_reduce_sum(sum, scratch);
+        // the three block sums share one barrier: every thread adds the
+        // four wave totals itself, in a fixed order
+        sum = wave_reduce_sum(sum);
+        dsum = wave_reduce_sum(dsum);
+        dsumsq = wave_reduce_sum(dsumsq);
+        if (lane == 0) {
+            scratch[0][wave] = sum;
+            scratch[1][wave] = dsum;
+            scratch[2][wave] = dsumsq;
+        }
         __syncthreads();
-        sumsq = block_reduce_sum(sumsq, scratch);
+        sum = (scratch[0][0] + scratch[0][2]) + (scratch[0][1] + scratch[0][3]);
+        dsum = (scratch[1][0] + scratch[1][2]) + (scratch[1][1] + scratch[1][3]);
+        dsumsq = (scratch[2][0] + scratch[2][2]) + (scratch[2][1] + scratch[2][3]);
 
         const float inv_n = 1.f / (hv * VEC);
         const float mean = sum * inv_n;
-        const float var = sumsq * inv_n - mean * mean;
+        const float dmean = dsum * inv_n;
+        const float var = fmaxf(dsumsq * inv_n - dmean * dmean, 0.f);
         const float rstd = rsqrtf(var + eps);
         if (threadIdx.x == 0) {
             mean_out[row] = mean;
@@ -92,6 +135,9 @@ std::vector<torch::Tensor> layernorm_fwd(
     const long H = x.size(-1);
     TORCH_CHECK(H % 8 == 0, "hidden size must be a multiple of 8");
     const long rows = x.numel() / H;
+    TORCH_CHECK(gamma.is_cuda() && beta.is_cuda()
+                && gamma.numel() == H && beta.numel() == H,
+                "gamma and beta must be CUDA tensors of H elements");
 
     auto y = torch::empty_like(x);
     auto f32 = x.options().dtype(torch::kFloat32);

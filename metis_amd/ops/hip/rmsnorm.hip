@@ -118,6 +118,8 @@ std::vector<torch::Tensor> rmsnorm_fwd(
     const long H = x.size(-1);
     TORCH_CHECK(H % 8 == 0);
     const long rows = x.numel() / H;
+    TORCH_CHECK(gamma.is_cuda() && gamma.numel() == H,
+                "gamma must be a CUDA tensor of H elements");
 
     auto y = torch::empty_like(x);
     auto rstd = torch::empty({rows}, x.options().dtype(torch::kFloat32));

@@ -62,7 +62,15 @@ torch::Tensor rope_apply(
     TORCH_CHECK(x.dim() == 4, "x must be [B, H, S, D]");
     const long D = x.size(3), S = x.size(2);
     TORCH_CHECK(D % 8 == 0, "head dim must be a multiple of 8");
-    TORCH_CHECK(cos_t.size(0) >= S && cos_t.size(1) == D / 2, "table mismatch");
+    TORCH_CHECK(cos_t.dim() == 2 && cos_t.size(0) >= S
+                && cos_t.size(1) == D / 2, "table mismatch");
+    TORCH_CHECK(sin_t.sizes() == cos_t.sizes(),
+                "cos and sin tables must have the same shape");
+    TORCH_CHECK(cos_t.is_cuda() && sin_t.is_cuda()
+                && cos_t.dtype() == torch::kFloat32
+                && sin_t.dtype() == torch::kFloat32
+                && cos_t.is_contiguous() && sin_t.is_contiguous(),
+                "cos/sin tables must be contiguous CUDA fp32");
     auto xc = x.contiguous();
     auto y = torch::empty_like(xc);
     const long rows = x.numel() / D;

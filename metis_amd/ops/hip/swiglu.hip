@@ -75,6 +75,12 @@ torch::Tensor swiglu_fwd(torch::Tensor a, torch::Tensor b) {
 
 std::vector<torch::Tensor> swiglu_bwd(
     torch::Tensor dy, torch::Tensor a, torch::Tensor b) {
+    TORCH_CHECK(dy.is_cuda() && a.is_cuda() && b.is_cuda(),
+                "swiglu bwd: dy, a and b must be CUDA tensors");
+    TORCH_CHECK(dy.dtype() == torch::kBFloat16 && a.dtype() == torch::kBFloat16
+                && b.dtype() == torch::kBFloat16, "swiglu bwd: bf16 only");
+    TORCH_CHECK(dy.numel() == a.numel() && b.numel() == a.numel()
+                && a.numel() % 8 == 0, "swiglu bwd: size mismatch");
     auto dyc = dy.contiguous(), ac = a.contiguous(), bc = b.contiguous();
     auto da = torch::empty_like(ac);
     auto db = torch::empty_like(bc);

@@ -26,6 +26,7 @@ EPS = 1e-5
 HIDDEN = (8, 512, 768, 2560, 4096, 8192)
 ROWS = (1, 3, 33, 257)
 CASES = [(r, h) for h in HIDDEN for r in ROWS] + [(5000, 512)]
+RMS_WIDE_CASES = [(r, h) for h in (8200, 12288, 16384) for r in (1, 3, 130)]
 
 
 @pytest.fixture(scope="module")
@@ -76,7 +77,7 @@ def test_layernorm_bwd_shapes(ext, rows, hidden):
         assert torch.equal(a, b)
 
 
-@pytest.mark.parametrize("rows,hidden", CASES)
+@pytest.mark.parametrize("rows,hidden", CASES + RMS_WIDE_CASES)
 def test_rmsnorm_bwd_shapes(ext, rows, hidden):
     x, dy, gamma = _inputs(rows, hidden)
     xf = x.float().requires_grad_(True)
