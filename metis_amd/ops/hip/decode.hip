@@ -118,6 +118,8 @@ __global__ __launch_bounds__(THREADS) void attn_decode_kernel(
 torch::Tensor attn_decode(torch::Tensor q, torch::Tensor k, torch::Tensor v,
                           double scale) {
     const AttnDims a = check_attn_qkv(q, k, v, /*decode=*/true);
+    // an empty cache has no softmax: the merge would write 0 * (1 / 0)
+    TORCH_CHECK(a.S >= 1, "attn_decode needs at least one key, got S = 0");
     auto qc = q.contiguous(), kc = k.contiguous(), vc = v.contiguous();
     auto out = torch::empty_like(qc);
     auto stream = c10::hip::getCurrentHIPStream().stream();

@@ -163,16 +163,10 @@ std::vector<torch::Tensor> layernorm_fwd(
 std::vector<torch::Tensor> layernorm_bwd(
     torch::Tensor dy, torch::Tensor x, torch::Tensor gamma,
     torch::Tensor mean, torch::Tensor rstd) {
-    TORCH_CHECK(dy.is_cuda() && dy.dtype() == torch::kBFloat16, "dy must be CUDA bf16");
-    TORCH_CHECK(x.is_contiguous() && mean.is_contiguous() && rstd.is_contiguous(),
-                "x, mean and rstd must be contiguous");
+    norm_bwd::check_args(dy, x, gamma, &mean, rstd, 8192, "layernorm bwd");
     auto dyc = dy.contiguous();
     const long H = x.size(-1);
     const long rows = x.numel() / H;
-    TORCH_CHECK(H % 8 == 0 && H <= 8192,
-                "layernorm bwd supports hidden size % 8 == 0, <= 8192");
-    TORCH_CHECK(rows >= 1 && dyc.numel() == x.numel() && mean.numel() == rows
-                && rstd.numel() == rows, "layernorm bwd: shape mismatch");
 
     auto dx = torch::empty_like(x);
     auto f32 = x.options().dtype(torch::kFloat32);

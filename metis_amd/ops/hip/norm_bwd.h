@@ -32,6 +32,39 @@ constexpr int VEC = 8;          // bf16 per lane per row (16 B)
 constexpr int MAX_WAVES = 16;   // 1024 threads = H 8192
 constexpr int MAX_SLABS = 1024;
 
+// Arguments of layernorm_bwd / rmsnorm_bwd (mean == nullptr). The kernels
+// read x and dy as [rows, H] bf16, H floats of gamma and `rows` floats of
+// mean and rstd, all through raw pointers: every one of those sizes,
+// dtypes and devices is pinned here, before anything is launched.
+inline void check_args(const torch::Tensor& dy, const torch::Tensor& x,
+                       const torch::Tensor& gamma, const torch::Tensor* mean,
+                       const torch::Tensor& rstd, long max_h, const char* op) {
+    TORCH_CHECK(x.is_cuda() && x.dtype() == torch::kBFloat16,
+                op, ": x must be CUDA bf16");
+    TORCH_CHECK(dy.is_cuda() && dy.dtype() == torch::kBFloat16,
+                op, ": dy must be CUDA bf16");
+    TORCH_CHECK(x.dim() >= 1 && x.is_contiguous(), op, ": x must be contiguous");
+    const long H = x.size(-1);
+    TORCH_CHECK(H > 0 && H % VEC == 0 && H <= max_h,
+                op, " supports hidden size % 8 == 0, <= ", max_h);
+    const long rows = x.numel() / H;
+    TORCH_CHECK(rows >= 1 && rows < (1L << 31), op, ": row count out of range");
+    TORCH_CHECK(dy.dim() >= 1 && dy.size(-1) == H && dy.numel() == x.numel(),
+                op, ": dy must have x's row length and row count");
+    TORCH_CHECK(gamma.is_cuda() && gamma.numel() == H,
+                op, ": gamma must be a CUDA tensor of H elements");
+    TORCH_CHECK(rstd.is_cuda() && rstd.dtype() == torch::kFloat32
+                && rstd.is_contiguous() && rstd.numel() == rows,
+                op, ": rstd must be a contiguous CUDA fp32 tensor, one per row");
+    if (mean)
+        TORCH_CHECK(mean->is_cuda() && mean->dtype() == torch::kFloat32
+                    && mean->is_contiguous() && mean->numel() == rows,
+                    op, ": mean must be a contiguous CUDA fp32 tensor, one per row");
+    for (const torch::Tensor* t : {&dy, &gamma, &rstd, mean})
+        TORCH_CHECK(!t || t->get_device() == x.get_device(),
+                    op, ": all arguments must be on x's device");
+}
+
 // RMS = false: LayerNorm, xhat = (x - mean) * rstd,
 //   dx = rstd * (dy*g - mean(dy*g) - xhat * mean(dy*g*xhat)), dgamma, dbeta.
 // RMS = true:  RMSNorm, xhat = x * rstd,

@@ -137,8 +137,18 @@ std::vector<torch::Tensor> qkv_split_transpose(
 
 torch::Tensor qkv_split_transpose_bwd(
     torch::Tensor dq, torch::Tensor dk, torch::Tensor dv, long head_dim) {
+    for (const torch::Tensor* t : {&dq, &dk, &dv})
+        TORCH_CHECK(t->is_cuda() && t->dtype() == torch::kBFloat16
+                    && t->dim() == 4 && t->get_device() == dq.get_device(),
+                    "dq, dk and dv must be 4-d CUDA bf16 on one device");
+    TORCH_CHECK(head_dim > 0 && head_dim % 8 == 0,
+                "head dim must be a positive multiple of 8");
     const long B = dq.size(0), nq = dq.size(1), S = dq.size(2);
     const long nkv = dk.size(1);
+    TORCH_CHECK(dq.size(3) == head_dim && dk.size(3) == head_dim,
+                "dq and dk must be [B, heads, S, head_dim]");
+    TORCH_CHECK(dk.size(0) == B && dk.size(2) == S && dv.sizes() == dk.sizes(),
+                "dk and dv must both be [B, nkv, S, head_dim] with dq's B and S");
     auto dqkv = torch::empty({B, S, (nq + 2 * nkv) * head_dim}, dq.options());
     const long chunks = dqkv.numel() / 8;
     hipLaunchKernelGGL(split_transpose_bwd_kernel, dim3(grid_for(chunks)),
@@ -170,6 +180,10 @@ torch::Tensor heads_merge(torch::Tensor x) {
 
 torch::Tensor heads_unmerge(torch::Tensor y, long H) {
     // [B, S, H*D] -> [B, H, S, D]
+    TORCH_CHECK(y.is_cuda() && y.dtype() == torch::kBFloat16 && y.dim() == 3,
+                "y must be a CUDA bf16 [B, S, H * D]");
+    TORCH_CHECK(H > 0 && y.size(2) % (H * 8) == 0,
+                "the last dimension must be H heads of D % 8 == 0");
     const long B = y.size(0), S = y.size(1), D = y.size(2) / H;
     auto x = torch::empty({B, H, S, D}, y.options());
     const long chunks = y.numel() / 8;

@@ -138,16 +138,10 @@ std::vector<torch::Tensor> rmsnorm_fwd(
 
 std::vector<torch::Tensor> rmsnorm_bwd(
     torch::Tensor dy, torch::Tensor x, torch::Tensor gamma, torch::Tensor rstd) {
-    TORCH_CHECK(dy.is_cuda() && dy.dtype() == torch::kBFloat16, "dy must be CUDA bf16");
-    TORCH_CHECK(x.is_contiguous() && rstd.is_contiguous(),
-                "x and rstd must be contiguous");
+    norm_bwd::check_args(dy, x, gamma, nullptr, rstd, 16384, "rmsnorm bwd");
     auto dyc = dy.contiguous();
     const long H = x.size(-1);
     const long rows = x.numel() / H;
-    TORCH_CHECK(H % 8 == 0 && H <= 16384,
-                "rmsnorm bwd supports hidden size % 8 == 0, <= 16384");
-    TORCH_CHECK(rows >= 1 && dyc.numel() == x.numel() && rstd.numel() == rows,
-                "rmsnorm bwd: shape mismatch");
 
     auto dx = torch::empty_like(x);
     auto f32 = x.options().dtype(torch::kFloat32);
