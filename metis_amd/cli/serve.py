@@ -19,6 +19,10 @@ batch between steps), whose padded ragged cache is read by the split-S
 ragged kernel (decode_ragged.hip) instead. ``--weight-dtype fp8`` quantises
 the linear weights once at load (e4m3fn, per-channel scales) and decodes
 through the weight-only fp8 kernel (w8_linear.hip); the default stays bf16.
+``--kv-dtype fp8`` (with ``--continuous`` only) holds the batcher's KV cache
+as e4m3fn bytes plus per-position scales (kv_quant.hip writes it,
+decode_ragged_fp8.hip reads it); the default stays bf16 and the two fp8
+options compose.
 """
 
 from __future__ import annotations
@@ -43,11 +47,12 @@ class BatcherWorker:
     retires; the loop steps whenever work is queued."""
 
     def __init__(self, model, capacity: int, max_batch: int = 8,
-                 device=None, eos_id=None):
+                 device=None, eos_id=None, kv_dtype: str = "bf16"):
         import threading
 
         self.cb = ContinuousBatcher(model, capacity, max_batch=max_batch,
-                                    device=device, eos_id=eos_id)
+                                    device=device, eos_id=eos_id,
+                                    kv_dtype=kv_dtype)
         self.lock = threading.Lock()
         self.events = {}
         self.results = {}
@@ -93,8 +98,10 @@ class BatcherWorker:
 
 
 def load_model(model_name: str, checkpoint: str = None,
-               dtype=torch.bfloat16, device=None, weight_dtype: str = "bf16"):
+               dtype=torch.bfloat16, device=None, weight_dtype: str = "bf16",
+               kv_dtype: str = "bf16"):
     assert weight_dtype in ("bf16", "fp8"), weight_dtype
+    assert kv_dtype in ("bf16", "fp8"), kv_dtype
     spec = MODEL_SPECS[model_name]
     cls = LlamaModel if isinstance(spec, LlamaModelSpec) else GPTModel
     model = cls(spec, dtype=dtype)
@@ -109,6 +116,7 @@ def load_model(model_name: str, checkpoint: str = None,
         quantize_for_decode(model)
     if device is not None:
         model = model.to(device)
+    model.kv_dtype = kv_dtype       # build_app's default for the batcher
     return model, spec
 
 
@@ -126,19 +134,27 @@ except ImportError:  # pragma: no cover - fastapi/pydantic are optional
 
 
 def build_app(model, spec, device=None, continuous: bool = False,
-              max_batch: int = 8):
+              max_batch: int = 8, kv_dtype: str = None):
     from fastapi import FastAPI
 
+    if kv_dtype is None:
+        kv_dtype = getattr(model, "kv_dtype", "bf16")
+    assert kv_dtype in ("bf16", "fp8"), kv_dtype
+    if kv_dtype == "fp8" and not continuous:
+        raise ValueError("kv_dtype='fp8' needs continuous=True: only the "
+                         "continuous batcher's ragged cache is quantised")
     app = FastAPI(title="metis_amd serve")
     worker = (BatcherWorker(model, spec.seq_length, max_batch=max_batch,
-                            device=device) if continuous else None)
+                            device=device, kv_dtype=kv_dtype)
+              if continuous else None)
     app.state.worker = worker
 
     @app.get("/health")
     def health():
         return {"status": "ok", "model": spec.name,
                 "seq_length": spec.seq_length,
-                "weight_dtype": weight_dtype_of(model)}
+                "weight_dtype": weight_dtype_of(model),
+                "kv_dtype": kv_dtype}
 
     @app.post("/generate")
     def gen(req: GenRequest):
@@ -181,7 +197,7 @@ def build_app(model, spec, device=None, continuous: bool = False,
     return app
 
 
-def main() -> None:
+def parse_args(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--model", default="gpt2-small", choices=sorted(MODEL_SPECS))
     p.add_argument("--checkpoint", default=None)
@@ -193,17 +209,29 @@ def main() -> None:
     p.add_argument("--max-batch", type=int, default=8)
     p.add_argument("--weight-dtype", choices=("bf16", "fp8"), default="bf16",
                    help="fp8: weight-only e4m3fn linears, quantised at load")
-    args = p.parse_args()
+    p.add_argument("--kv-dtype", choices=("bf16", "fp8"), default="bf16",
+                   help="fp8: e4m3fn KV cache with per-position scales "
+                        "(needs --continuous)")
+    args = p.parse_args(argv)
+    if args.kv_dtype == "fp8" and not args.continuous:
+        p.error("--kv-dtype fp8 requires --continuous")
+    return args
+
+
+def main() -> None:
+    args = parse_args()
 
     device = "cuda:0" if torch.cuda.is_available() else None
     dtype = torch.bfloat16 if torch.cuda.is_available() else torch.float32
     model, spec = load_model(args.model, args.checkpoint, dtype, device,
-                             weight_dtype=args.weight_dtype)
+                             weight_dtype=args.weight_dtype,
+                             kv_dtype=args.kv_dtype)
 
     import uvicorn
 
     uvicorn.run(build_app(model, spec, device, continuous=args.continuous,
-                          max_batch=args.max_batch), host=args.host,
+                          max_batch=args.max_batch,
+                          kv_dtype=args.kv_dtype), host=args.host,
                 port=args.port, log_level="warning")
 
 

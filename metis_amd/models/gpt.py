@@ -363,7 +363,14 @@ class GPTBlock(nn.Module):
             k, v = cache.append(layer_idx, k, v)
             if hasattr(cache, "kv_lens") and q.size(2) == 1:
                 # ragged cache: per-row lengths, padded views as they are
-                attn = decode_attention(q, k, v, kv_lens=cache.kv_lens())
+                scales = getattr(cache, "kv_scales", None)
+                scales = scales(layer_idx) if scales is not None else None
+                if scales is None:
+                    attn = decode_attention(q, k, v, kv_lens=cache.kv_lens())
+                else:           # fp8 cache: k, v are e4m3 bytes
+                    attn = decode_attention(q, k, v, kv_lens=cache.kv_lens(),
+                                            k_scale=scales[0],
+                                            v_scale=scales[1])
             else:
                 am = getattr(cache, "attention_mask", None)
                 mask = am(k.size(2), q.device) if am is not None else None

@@ -122,7 +122,14 @@ class LlamaBlock(nn.Module):
             if ragged:
                 # ragged cache: per-row lengths, padded views as they
                 # are, GQA mapped inside (no repeat_interleave copies)
-                attn = decode_attention(q, k, v, kv_lens=cache.kv_lens())
+                scales = getattr(cache, "kv_scales", None)
+                scales = scales(layer_idx) if scales is not None else None
+                if scales is None:
+                    attn = decode_attention(q, k, v, kv_lens=cache.kv_lens())
+                else:           # fp8 cache: k, v are e4m3 bytes
+                    attn = decode_attention(q, k, v, kv_lens=cache.kv_lens(),
+                                            k_scale=scales[0],
+                                            v_scale=scales[1])
             elif rag_mask is not None:
                 rep = hq // hkv
                 attn = F.scaled_dot_product_attention(

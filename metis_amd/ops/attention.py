@@ -166,8 +166,19 @@ def _ragged_supported(q: torch.Tensor, k: torch.Tensor) -> bool:
             and hkv > 0 and h % hkv == 0 and h // hkv in (1, 2, 4, 8))
 
 
+def _ragged_fp8_supported(q: torch.Tensor, k8: torch.Tensor) -> bool:
+    """Shapes decode_ragged_fp8.hip is instantiated for."""
+    h, hkv = q.size(1), k8.size(1)
+    return (q.is_cuda and q.dtype == torch.bfloat16
+            and k8.dtype == torch.float8_e4m3fn and q.size(2) == 1
+            and _head_dim_supported(q.size(-1))
+            and hkv > 0 and h % hkv == 0 and h // hkv in (1, 2, 4, 8))
+
+
 def decode_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
-                     kv_lens: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     kv_lens: Optional[torch.Tensor] = None,
+                     k_scale: Optional[torch.Tensor] = None,
+                     v_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Single-query attention over cached K/V (serving decode step):
     q [B, H, 1, D] vs k/v [B, Hkv, S, D], GQA mapped in-kernel. The
     gfx950 kernel (decode.hip) is the DEFAULT on supported shapes —
@@ -181,11 +192,38 @@ def decode_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     in place and never loads the padding; anything else builds the
     length mask and calls SDPA (which needs kv_lens >= 1: a fully masked
     row is NaN there, where the kernel writes zeros). METIS_DECODE_SPLIT=1 routes the dense
-    case through the split-S kernel too (A/B timing; off by default)."""
+    case through the split-S kernel too (A/B timing; off by default).
+
+    ``k_scale`` / ``v_scale`` fp32 [B, Hkv, S] (fp8 KV cache, ops/kv8.py;
+    both or neither, and only together with ``kv_lens``): k and v are
+    float8_e4m3fn and row j stands for ``scale_j * x8_j``. Supported
+    shapes run decode_ragged_fp8.hip, which applies the scales to the
+    score and the probability and never loads the padding; anything else
+    dequantises the valid prefix in q's dtype and takes the length-mask
+    SDPA computation below (padding bytes and scales are masked out
+    before they are multiplied)."""
     import os
 
     kernel_on = os.environ.get("METIS_DECODE_KERNEL", "1") == "1"
     scale = 1.0 / math.sqrt(q.size(-1))
+    if (k_scale is None) != (v_scale is None):
+        raise ValueError("k_scale and v_scale must be given together")
+    if k_scale is not None:
+        if kv_lens is None:
+            raise ValueError("an fp8 cache (k_scale/v_scale) needs kv_lens")
+        if kernel_on and _ragged_fp8_supported(q, k):
+            ext = _ops.require_extension()
+            lens = kv_lens.to(device=q.device, dtype=torch.int32)
+            return ext.attn_decode_ragged_fp8(q, k, v, k_scale, v_scale,
+                                              lens, scale)
+        cols = torch.arange(k.size(2), device=q.device)
+        keep = (cols[None] < kv_lens.to(q.device)[:, None])[:, None, :, None]
+        # mask bytes and scales separately: a padding byte may be NaN
+        # (0x7F) and a padding scale NaN, and 0 * NaN is NaN
+        ks = torch.where(keep[..., 0], k_scale, 0)[..., None]
+        vs = torch.where(keep[..., 0], v_scale, 0)[..., None]
+        k = (torch.where(keep, k.float(), 0) * ks).to(q.dtype)
+        v = (torch.where(keep, v.float(), 0) * vs).to(q.dtype)
     if kv_lens is not None:
         if kernel_on and _ragged_supported(q, k):
             ext = _ops.require_extension()

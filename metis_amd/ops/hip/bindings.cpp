@@ -18,6 +18,14 @@ torch::Tensor attn_decode(
 torch::Tensor attn_decode_ragged(
     torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor kv_lens,
     double scale, long num_splits);
+torch::Tensor attn_decode_ragged_fp8(
+    torch::Tensor q, torch::Tensor k8, torch::Tensor v8,
+    torch::Tensor k_scale, torch::Tensor v_scale, torch::Tensor kv_lens,
+    double scale, long num_splits);
+void kv_quant_store(
+    torch::Tensor k, torch::Tensor v, torch::Tensor k8, torch::Tensor v8,
+    torch::Tensor k_scale, torch::Tensor v_scale, torch::Tensor slots,
+    torch::Tensor pos);
 torch::Tensor w8_linear(
     torch::Tensor x, torch::Tensor w8, torch::Tensor scale,
     c10::optional<torch::Tensor> bias, long num_splits);
@@ -126,6 +134,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           pybind11::arg("q"), pybind11::arg("k"), pybind11::arg("v"),
           pybind11::arg("kv_lens"), pybind11::arg("scale"),
           pybind11::arg("num_splits") = 0);
+    m.def("attn_decode_ragged_fp8", &attn_decode_ragged_fp8,
+          "ragged split-S single-query attention over an fp8 (e4m3fn) K/V "
+          "cache with one fp32 scale per (batch row, kv head, position)",
+          pybind11::arg("q"), pybind11::arg("k8"), pybind11::arg("v8"),
+          pybind11::arg("k_scale"), pybind11::arg("v_scale"),
+          pybind11::arg("kv_lens"), pybind11::arg("scale"),
+          pybind11::arg("num_splits") = 0);
+    m.def("kv_quant_store", &kv_quant_store,
+          "quantise bf16 K/V rows [N,Hkv,T,D] to e4m3fn + per-row fp32 scale "
+          "and store them at position pos[n] + t of cache row slots[n]",
+          pybind11::arg("k"), pybind11::arg("v"), pybind11::arg("k8"),
+          pybind11::arg("v8"), pybind11::arg("k_scale"),
+          pybind11::arg("v_scale"), pybind11::arg("slots"),
+          pybind11::arg("pos"));
     m.def("w8_linear", &w8_linear,
           "fp8 (e4m3fn) weight-only linear for 1 <= M <= 16 bf16 rows: "
           "scale[n] * (x @ w8^T) + bias, fp32 accumulation, split-K",

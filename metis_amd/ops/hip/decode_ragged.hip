@@ -30,50 +30,12 @@
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
 
-#include <algorithm>
-
 #include "attn_host.h"
-#include "common.h"
+#include "decode_ragged_common.h"
 
 namespace {
 
-constexpr int THREADS = 256;
-constexpr int NWAVE = THREADS / WAVE_SIZE;
 constexpr int UNROLL = 4;          // rows in flight per lane group
-constexpr int COMBINE_THREADS = 128;
-constexpr float NEG_BIG = -1e30f;
-
-typedef unsigned int uintx4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void unpack8(bf16x8 raw, float* f) {
-    const uintx4 w = __builtin_bit_cast(uintx4, raw);
-    #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        f[2 * i] = __uint_as_float(w[i] << 16);
-        f[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-    }
-}
-
-// Cross-lane read inside a 16-lane DPP row (no LDS traffic, unlike the
-// ds_bpermute behind __shfl_xor). Controls: quad_perm [1,0,3,2] and
-// [2,3,0,1] (xor 1, xor 2), row_half_mirror (lane i <- 7-i of its 8),
-// row_mirror (lane i <- 15-i of its 16).
-template <int CTRL>
-__device__ __forceinline__ float dpp_read(float x) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(
-        0, __float_as_int(x), CTRL, 0xf, 0xf, true));
-}
-
-// Sum over the LPR (8 or 16) aligned lanes that share a K/V row; every
-// lane of the group ends with the total.
-template <int LPR>
-__device__ __forceinline__ float group_sum(float x) {
-    x += dpp_read<0xB1>(x);
-    x += dpp_read<0x4E>(x);
-    x += dpp_read<0x141>(x);      // quad sums are lane-uniform: mirror = other quad
-    if (LPR == 16) x += dpp_read<0x140>(x);
-    return x;
-}
 
 template <int D, int G>
 __global__ __launch_bounds__(THREADS) void attn_decode_ragged_kernel(
@@ -244,42 +206,12 @@ __global__ __launch_bounds__(THREADS) void attn_decode_ragged_kernel(
     }
 }
 
-// One workgroup per (b, h): thread d merges element d of the partials.
-__global__ __launch_bounds__(COMBINE_THREADS) void attn_decode_combine_kernel(
-    const float* __restrict__ ws_acc,   // [B*H, num_splits, D]
-    const float* __restrict__ ws_ml,    // [B*H, num_splits, 2]
-    short* __restrict__ Out,            // [B*H, D]
-    int D, int num_splits) {
-    const long bh = blockIdx.x;
-    const int d = threadIdx.x;
-    if (d >= D) return;
-    const float* ml = ws_ml + bh * num_splits * 2;
-    float gm = NEG_BIG;
-    for (int s = 0; s < num_splits; ++s) gm = fmaxf(gm, ml[2 * s]);
-    float gl = 0.f, ga = 0.f;
-    for (int s = 0; s < num_splits; ++s) {
-        const float w = __expf(ml[2 * s] - gm);
-        gl += ml[2 * s + 1] * w;
-        ga += ws_acc[(bh * num_splits + s) * D + d] * w;
-    }
-    Out[bh * D + d] = float_to_bf16_bits(gl > 0.f ? ga / gl : 0.f);
-}
-
 // Rows contiguous, 16-byte aligned base and batch/head strides: the
 // kernel can read the view in place.
 bool readable_in_place(const torch::Tensor& t, long D) {
     return t.stride(3) == 1 && t.stride(2) == D
         && t.stride(0) % 8 == 0 && t.stride(1) % 8 == 0
         && reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
-}
-
-// Host-side split count from shapes only (no device sync): about two
-// workgroups per CU, each split at least MIN_ROWS rows.
-int auto_num_splits(long B, long Hkv, long S) {
-    constexpr long TARGET_WG = 2 * 256, MIN_ROWS = 256, MAX_SPLITS = 64;
-    const long want = (TARGET_WG + B * Hkv - 1) / (B * Hkv);
-    const long fit = std::max<long>(S / MIN_ROWS, 1);
-    return (int)std::min({want, fit, MAX_SPLITS});
 }
 
 }  // namespace

@@ -9,6 +9,14 @@ GPU a one-token step runs a hand-written single-query kernel through
 split-S ragged kernel (decode_ragged.hip) for ``RaggedKVCache``, which
 reads the padded buffers in place with per-row lengths. Prefill chunks
 and unsupported shapes use SDPA over the cache.
+
+``kv_dtype="fp8"`` (RaggedKVCache, generate_ragged, ContinuousBatcher;
+default "bf16") holds the ragged cache as e4m3fn bytes plus one fp32
+scale per (row, kv head, position) — the format of ops/kv8.py, D + 4
+bytes per vector instead of 2 D. Every write goes through
+``kv_quant_store`` (kv_quant.hip on the GPU) and a decode step reads it
+with decode_ragged_fp8.hip. Prefill still runs on an exact ``KVCache``;
+only what is stored into the ragged cache is quantised.
 """
 
 from __future__ import annotations
@@ -17,6 +25,8 @@ from typing import Optional
 
 import torch
 import torch.distributed as dist
+
+from metis_amd.ops.kv8 import KV_DTYPES, kv_quant_store
 
 
 class KVCache:
@@ -44,21 +54,58 @@ class RaggedKVCache:
     """Padded per-block K/V buffers for a decode batch whose sequences
     have DIFFERENT lengths: row i's valid prefix is lengths[i], new
     tokens land at per-row positions, and attention_mask() hides the
-    padding. Built by generate_ragged() from per-sequence prefills."""
+    padding. Built by generate_ragged() from per-sequence prefills.
 
-    def __init__(self, lengths: torch.Tensor):
+    ``kv_dtype="fp8"``: a layer is (k8, v8, k_scale, v_scale) — e4m3fn
+    [b, h, cap, d] and fp32 [b, h, cap] (ops/kv8.py). append() quantises
+    the new token at the per-row positions before attention reads it and
+    returns the fp8 views; kv_scales() hands the matching scale views to
+    decode_attention."""
+
+    def __init__(self, lengths: torch.Tensor, kv_dtype: str = "bf16"):
+        assert kv_dtype in KV_DTYPES, kv_dtype
         self.lengths = lengths.clone()          # [b] current per-row length
+        self.kv_dtype = kv_dtype
         self._kv = {}
+        self._upto = 0      # columns handed out by the last append()
+
+    def _alloc_fp8(self, idx: int, b: int, h: int, cap: int, d: int,
+                   device) -> None:
+        def bytes_():
+            return torch.zeros(b, h, cap, d, dtype=torch.uint8,
+                               device=device).view(torch.float8_e4m3fn)
+
+        def scales():
+            return torch.zeros(b, h, cap, dtype=torch.float32, device=device)
+
+        self._kv[idx] = (bytes_(), bytes_(), scales(), scales())
+
+    def store(self, layer_idx: int, k: torch.Tensor, v: torch.Tensor,
+              slots: torch.Tensor, pos: torch.Tensor) -> None:
+        """fp8 only: quantise k, v [n, h, t, d] into rows ``slots`` at
+        positions ``pos`` + 0..t-1 (one kv_quant_store call)."""
+        k8, v8, ks, vs = self._kv[layer_idx]
+        kv_quant_store(k, v, k8, v8, ks, vs, slots.to(k8.device),
+                       pos.to(k8.device))
 
     @classmethod
-    def from_prefills(cls, caches, lengths, max_new: int):
+    def from_prefills(cls, caches, lengths, max_new: int,
+                      kv_dtype: str = "bf16"):
         """Merge per-sequence KVCache objects (batch 1 each) into padded
         [b, h, max_len + max_new, d] buffers."""
-        self = cls(torch.as_tensor(lengths))
+        self = cls(torch.as_tensor(lengths), kv_dtype)
         b = len(caches)
         total = int(self.lengths.max()) + max_new
         for idx in caches[0]._kv:
             k0, v0 = caches[0]._kv[idx]
+            if kv_dtype == "fp8":
+                self._alloc_fp8(idx, b, k0.size(1), total, k0.size(3),
+                                k0.device)
+                for i, c in enumerate(caches):
+                    k, v = c._kv[idx]
+                    self.store(idx, k, v, torch.tensor([i]),
+                               torch.tensor([0]))
+                continue
             kbuf = k0.new_zeros(b, k0.size(1), total, k0.size(3))
             vbuf = torch.zeros_like(kbuf)
             for i, c in enumerate(caches):
@@ -70,12 +117,26 @@ class RaggedKVCache:
 
     def append(self, layer_idx: int, k: torch.Tensor, v: torch.Tensor):
         assert k.size(2) == 1, "ragged cache decodes one token at a time"
+        if self.kv_dtype == "fp8":
+            self.store(layer_idx, k, v,
+                       torch.arange(k.size(0), device=k.device), self.lengths)
+            k8, v8, _, _ = self._kv[layer_idx]
+            self._upto = int(self.lengths.max()) + 1
+            return k8[:, :, :self._upto], v8[:, :, :self._upto]
         kbuf, vbuf = self._kv[layer_idx]
         rows = torch.arange(k.size(0), device=k.device)
         kbuf[rows, :, self.lengths] = k[:, :, 0]
         vbuf[rows, :, self.lengths] = v[:, :, 0]
         upto = int(self.lengths.max()) + 1
         return kbuf[:, :, :upto], vbuf[:, :, :upto]
+
+    def kv_scales(self, layer_idx: int):
+        """None for a bf16 cache; for fp8 the (k_scale, v_scale) views
+        [b, h, upto] that go with what append() just returned."""
+        if self.kv_dtype != "fp8":
+            return None
+        _, _, ks, vs = self._kv[layer_idx]
+        return ks[:, :, :self._upto], vs[:, :, :self._upto]
 
     def attention_mask(self, total: int, device) -> torch.Tensor:
         """[b, 1, 1, total] bool: row i may attend cols <= lengths[i]
@@ -106,11 +167,13 @@ def generate_ragged(
     top_k: int = 0,
     generator: Optional[torch.Generator] = None,
     device=None,
+    kv_dtype: str = "bf16",
 ):
     """Batched decoding of prompts with different lengths: each prompt is
     prefilled separately (exact per-sequence caches), then all rows
-    decode together against a padded ragged cache. Returns a list of
-    token lists (prompt + continuation). Single process (tp=pp=1)."""
+    decode together against a padded ragged cache (``kv_dtype="fp8"``:
+    quantised as it is stored). Returns a list of token lists (prompt +
+    continuation). Single process (tp=pp=1)."""
     model.eval()
     lengths = [len(p) for p in prompts]
     caches, last = [], []
@@ -120,7 +183,8 @@ def generate_ragged(
         logits = model(toks, cache=c, pos_offset=0)
         caches.append(c)
         last.append(logits[0, -1])
-    cache = RaggedKVCache.from_prefills(caches, lengths, max_new_tokens)
+    cache = RaggedKVCache.from_prefills(caches, lengths, max_new_tokens,
+                                        kv_dtype=kv_dtype)
     if device is not None:
         cache.lengths = cache.lengths.to(device)
     logits = torch.stack(last)                   # [b, vocab]
@@ -205,10 +269,19 @@ class ContinuousBatcher:
     models: it takes ``cache.kv_lens()`` and the ``[:, :, :upto]``
     buffer views as they are. METIS_DECODE_KERNEL=0, CPU and
     unsupported shapes take the length-mask SDPA path instead.
+
+    ``kv_dtype="fp8"`` keeps the shared buffers as e4m3fn bytes plus
+    per-position fp32 scales (ops/kv8.py): about 0.52x the cache memory.
+    Prefills stay exact; the splice into a slot and every decode append
+    quantise through ``kv_quant_store``, and the step's attention runs
+    decode_ragged_fp8.hip.
     """
 
     def __init__(self, model, capacity: int, max_batch: int = 8,
-                 device=None, eos_id: Optional[int] = None):
+                 device=None, eos_id: Optional[int] = None,
+                 kv_dtype: str = "bf16"):
+        assert kv_dtype in KV_DTYPES, kv_dtype
+        self.kv_dtype = kv_dtype
         self.model = model
         self.capacity = capacity
         self.max_batch = max_batch
@@ -242,9 +315,14 @@ class ContinuousBatcher:
         if self.cache is not None:
             return
         self.cache = RaggedKVCache(torch.zeros(self.max_batch,
-                                               dtype=torch.long))
+                                               dtype=torch.long),
+                                   self.kv_dtype)
         self.cache.active = torch.zeros(self.max_batch, dtype=torch.bool)
         for idx, (k, v) in proto_cache._kv.items():
+            if self.kv_dtype == "fp8":
+                self.cache._alloc_fp8(idx, self.max_batch, k.size(1),
+                                      self.capacity, k.size(3), k.device)
+                continue
             kbuf = k.new_zeros(self.max_batch, k.size(1), self.capacity,
                                k.size(3))
             self.cache._kv[idx] = (kbuf, torch.zeros_like(kbuf))
@@ -263,6 +341,10 @@ class ContinuousBatcher:
             self._ensure_cache(pre)
             plen = len(req["prompt"])
             for idx, (k, v) in pre._kv.items():
+                if self.kv_dtype == "fp8":
+                    self.cache.store(idx, k, v, torch.tensor([slot]),
+                                     torch.tensor([0]))
+                    continue
                 kbuf, vbuf = self.cache._kv[idx]
                 kbuf[slot, :, :plen] = k[0]
                 vbuf[slot, :, :plen] = v[0]

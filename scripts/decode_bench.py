@@ -11,14 +11,22 @@ Two further modes:
              ext.attn_decode_ragged (decode_ragged.hip) over a shape grid,
              alternating the two; prints microseconds, achieved bytes/s
              (bytes needed = 2 * sum_b kv_len_b * Hkv * D * 2) and that as
-             a share of the 6.3 TB/s achievable HBM bandwidth.
+             a share of the 6.3 TB/s achievable HBM bandwidth. With
+             --kv-dtype fp8 the fp8-cache kernel (decode_ragged_fp8.hip)
+             runs on the same K/V quantised per row, alternated call by
+             call with the other two (bytes needed = 2 * sum_b kv_len_b *
+             Hkv * (D + 4)); its speedup column is against the bf16 ragged
+             kernel.
   --ragged   the continuous-batching workload (llama3-1b, 8 requests,
              prompts 64-183 tokens, 32 new each, ContinuousBatcher), once
              per METIS_DECODE_KERNEL value in fresh child processes,
              alternated; prints tok/s per repeat and the spread. With
              --ab-weights the two arms are bf16 and fp8 weights instead
              (METIS_DECODE_KERNEL left alone), and peak allocated memory
-             is reported per arm.
+             is reported per arm. With --ab-kv the two arms are a bf16 and
+             an fp8 KV cache (ContinuousBatcher kv_dtype) in the same way;
+             --long-context swaps the workload for 8 prompts of 3072-3968
+             tokens in a cache of capacity 4096.
   --linear   device-event timing of the fp8 weight-only decode linear
              (w8_linear.hip) against bf16 F.linear (hipBLASLt) on the
              llama3-1b / llama3-8b linears at M in {1, 4, 8, 16}, the two
@@ -79,10 +87,14 @@ def _time_alternating(fns, iters, warmup):
 def kernel_mode(args):
     from metis_amd.ops import require_extension
 
+    from metis_amd.ops.kv8 import quantize_kv_e4m3
+
     ext = require_extension()
     torch.manual_seed(0)
+    fp8 = args.kv_dtype == "fp8"
     print("kernel  B   H Hkv   D      S  lens     |   dense us  TB/s  %HBM |"
-          "  ragged us  TB/s  %HBM  splits=auto | speedup")
+          "  ragged us  TB/s  %HBM  splits=auto | speedup"
+          + (" |     fp8 us  TB/s  %HBM | fp8 vs ragged" if fp8 else ""))
 
     def report(B, H, Hkv, D, S, lens_list, tag):
         q = torch.randn(B, H, 1, D, device="cuda", dtype=torch.bfloat16)
@@ -95,16 +107,25 @@ def kernel_mode(args):
         dense = tag == "full"     # decode.hip has no per-row length
         if dense:
             fns.insert(0, lambda: ext.attn_decode(q, k, v, scale))
+        if fp8:
+            k8, ks = quantize_kv_e4m3(k)
+            v8, vs = quantize_kv_e4m3(v)
+            need8 = 2 * sum(lens_list) * Hkv * (D + 4)   # bytes + scales
+            fns.append(lambda: ext.attn_decode_ragged_fp8(
+                q, k8, v8, ks, vs, lens, scale))
         us = _time_alternating(fns, args.iters, args.warmup)
+        rag = us[1] if dense else us[0]
 
-        def cols(t):
+        def cols(t, need=need):
             bps = need / (t * 1e-6)
             return f"{t:10.1f} {bps / 1e12:5.2f} {100 * bps / HBM_ACHIEVABLE:5.1f}"
 
         d = cols(us[0]) if dense else " " * 10 + "  n/a   n/a"
-        sp = f"{us[0] / us[-1]:6.2f}x" if dense else "   n/a"
+        sp = f"{us[0] / rag:6.2f}x" if dense else "   n/a"
+        f8 = (f" | {cols(us[-1], need8)} | {rag / us[-1]:6.2f}x"
+              if fp8 else "")
         print(f"kernel {B:2d} {H:3d} {Hkv:3d} {D:3d} {S:6d}  {tag:8s} | {d} | "
-              f"{cols(us[-1])}              | {sp}", flush=True)
+              f"{cols(rag)}              | {sp}{f8}", flush=True)
 
     for H, Hkv, D in ((32, 8, 64), (32, 8, 128)):
         for B in (1, 8, 64):
@@ -240,13 +261,17 @@ def _ragged_child(args):
         torch.cuda.empty_cache()
     torch.cuda.reset_peak_memory_stats()
     g = torch.Generator().manual_seed(0)
-    prompts = [torch.randint(0, spec.vocab_size, (64 + 17 * i,),
-                             generator=g).tolist() for i in range(8)]
+    if args.long_context:       # multiples of 128: flash-attention prefill
+        plens, capacity = [3072 + 128 * i for i in range(8)], 4096
+    else:
+        plens, capacity = [64 + 17 * i for i in range(8)], 256
+    prompts = [torch.randint(0, spec.vocab_size, (n,),
+                             generator=g).tolist() for n in plens]
     new = 32
 
     def run():
-        cb = ContinuousBatcher(model, capacity=256, max_batch=8,
-                               device="cuda")
+        cb = ContinuousBatcher(model, capacity=capacity, max_batch=8,
+                               device="cuda", kv_dtype=args.kv_dtype)
         for p in prompts:
             cb.submit(p, new, temperature=0.0)
         torch.cuda.synchronize()
@@ -266,11 +291,12 @@ def _ragged_child(args):
           flush=True)
 
 
-def _run_child(args, env, weight_dtype):
+def _run_child(args, env, weight_dtype, kv_dtype="bf16"):
     out = subprocess.run(
         [sys.executable, os.path.abspath(__file__), "--ragged-child",
          "--inner", str(args.inner), "--model", args.model,
-         "--weight-dtype", weight_dtype],
+         "--weight-dtype", weight_dtype, "--kv-dtype", kv_dtype]
+        + (["--long-context"] if args.long_context else []),
         env=env, check=True, capture_output=True, text=True).stdout
     line = [ln for ln in out.splitlines() if ln.startswith(RESULT_TAG)][-1]
     return json.loads(line[len(RESULT_TAG):])
@@ -283,7 +309,7 @@ def ragged_weights_mode(args):
     peaks = {"bf16": [], "fp8": []}
     for rep in range(args.repeats):
         for wd in ("bf16", "fp8"):
-            res = _run_child(args, dict(os.environ), wd)
+            res = _run_child(args, dict(os.environ), wd, args.kv_dtype)
             med = statistics.median(res["tok_s"])
             results[wd].append(med)
             peaks[wd].append(res["peak_gib"])
@@ -301,6 +327,34 @@ def ragged_weights_mode(args):
           f"tok/s vs bf16 (opt-in either way: fp8 changes the numerics)")
 
 
+def ragged_kv_mode(args):
+    """Parent: never touches the GPU; one fresh child per measurement,
+    alternating a bf16 and an fp8 KV cache (weights as --weight-dtype)."""
+    results = {"bf16": [], "fp8": []}
+    peaks = {"bf16": [], "fp8": []}
+    ctx = "long-context " if args.long_context else ""
+    for rep in range(args.repeats):
+        for kd in ("bf16", "fp8"):
+            res = _run_child(args, dict(os.environ), args.weight_dtype, kd)
+            med = statistics.median(res["tok_s"])
+            results[kd].append(med)
+            peaks[kd].append(res["peak_gib"])
+            print(f"ragged {ctx}{args.model} repeat {rep} kv={kd}: median "
+                  f"{med:.1f} tok/s of {[round(t, 1) for t in res['tok_s']]}, "
+                  f"peak {res['peak_gib']:.2f} GiB", flush=True)
+    for kd in ("bf16", "fp8"):
+        r = results[kd]
+        print(f"ragged {ctx}{args.model} weights={args.weight_dtype} kv={kd}: "
+              f"median {statistics.median(r):.1f} tok/s, spread "
+              f"{max(r) - min(r):.1f} (min {min(r):.1f}, max {max(r):.1f}) "
+              f"over {len(r)} processes, peak allocated "
+              f"{max(peaks[kd]):.2f} GiB")
+    gain = statistics.median(results["fp8"]) / statistics.median(results["bf16"])
+    print(f"ragged {ctx}{args.model} verdict: fp8 KV cache "
+          f"{100 * (gain - 1):+.1f}% tok/s vs bf16 (opt-in either way: fp8 "
+          f"changes the numerics)")
+
+
 def ragged_mode(args):
     """Parent: never touches the GPU; starts one fresh child per
     measurement, alternating METIS_DECODE_KERNEL=0 / 1."""
@@ -308,7 +362,8 @@ def ragged_mode(args):
     for rep in range(args.repeats):
         for flag in ("0", "1"):
             env = dict(os.environ, METIS_DECODE_KERNEL=flag)
-            tps = _run_child(args, env, args.weight_dtype)["tok_s"]
+            tps = _run_child(args, env, args.weight_dtype,
+                             args.kv_dtype)["tok_s"]
             med = statistics.median(tps)
             results[flag].append(med)
             print(f"ragged repeat {rep} METIS_DECODE_KERNEL={flag}: "
@@ -353,6 +408,15 @@ def main():
     ap.add_argument("--ab-weights", action="store_true",
                     help="--ragged: alternate bf16 / fp8 weights instead of "
                          "METIS_DECODE_KERNEL")
+    ap.add_argument("--kv-dtype", choices=("bf16", "fp8"), default="bf16",
+                    help="--kernel: add the fp8-cache kernel's columns; "
+                         "--ragged: KV cache of the ContinuousBatcher")
+    ap.add_argument("--ab-kv", action="store_true",
+                    help="--ragged: alternate a bf16 / fp8 KV cache instead "
+                         "of METIS_DECODE_KERNEL")
+    ap.add_argument("--long-context", action="store_true",
+                    help="--ragged: 8 prompts of 3072-3968 tokens, capacity "
+                         "4096, instead of 64-183 tokens in 256")
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--repeats", type=int, default=3)
@@ -373,6 +437,8 @@ def main():
         assert args.repeats >= 3, "--ragged needs at least 3 repeats"
         if args.ab_weights:
             return ragged_weights_mode(args)
+        if args.ab_kv:
+            return ragged_kv_mode(args)
         return ragged_mode(args)
 
     spec = MODEL_SPECS[args.model]

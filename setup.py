@@ -33,6 +33,8 @@ sources = [
     os.path.join(HIP_DIR, "qkv_rope.hip"),
     os.path.join(HIP_DIR, "decode.hip"),
     os.path.join(HIP_DIR, "decode_ragged.hip"),
+    os.path.join(HIP_DIR, "decode_ragged_fp8.hip"),
+    os.path.join(HIP_DIR, "kv_quant.hip"),
     os.path.join(HIP_DIR, "w8_linear.hip"),
     os.path.join(HIP_DIR, "lt_gemm.cpp"),
 ]
