@@ -24,6 +24,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from metis_amd.ops import LayerNorm
+from metis_amd.ops import residual as _res
 from metis_amd.ops.attention import decode_attention, packed_flash_attention
 from metis_amd.ops.cross_entropy import cross_entropy
 from metis_amd.ops.mlp import fused_mlp
@@ -346,6 +347,29 @@ class GPTBlock(nn.Module):
         mask = torch.tril(mask, diagonal=total - new)
         return F.scaled_dot_product_attention(q, k, v, attn_mask=mask)
 
+    def _forward_fused(self, x: torch.Tensor, tp_group) -> torch.Tensor:
+        """The default training path (bf16 on the GPU, no sp) with the
+        bias, residual and LayerNorm passes fused (ops/residual.py). Same
+        values as the eager path below: x = residual + (linear + bias) with
+        both roundings, the bias added after the TP reduce."""
+        x, y = _res.norm_passthrough(
+            x, self.ln_attn.weight, self.ln_attn.bias, self.ln_attn.eps)
+        qkv = self.qkv(y, tp_group)
+        attn = packed_flash_attention(
+            qkv, self.heads_per_rank, self.heads_per_rank, self.head_dim
+        )
+        part = _ReduceFromTP.apply(F.linear(attn, self.proj.weight), tp_group)
+        x, y = _res.bias_residual_layer_norm(
+            part, self.proj.bias, x, self.ln_mlp.weight, self.ln_mlp.bias,
+            self.ln_mlp.eps)
+        # the GEMM adds fc1.bias as before; its gradient comes from the
+        # GeLU backward instead of a column reduce over dh
+        h = F.linear(_CopyToTP.apply(y, tp_group), self.fc1.weight,
+                     self.fc1.bias.detach())
+        a = _res.gelu_bgrad(h, self.fc1.bias)
+        part = _ReduceFromTP.apply(F.linear(a, self.fc2.weight), tp_group)
+        return _res.bias_residual_add(part, self.fc2.bias, x)
+
     def forward(self, x: torch.Tensor, tp_group, sp: bool = False,
                 cache=None, layer_idx: int = 0) -> torch.Tensor:
         """With ``sp`` the block holds [b, s/tp, h] in the norm/residual
@@ -380,6 +404,15 @@ class GPTBlock(nn.Module):
             y = self.fc1(self.ln_mlp(x), tp_group)
             x = residual + self.fc2(F.gelu(y, approximate="tanh"), tp_group)
             return x
+
+        if (not sp and not self._lt_mlp and _res.fused_enabled(x)
+                # plain bf16 linears only (not the fp8 serving modules)
+                and isinstance(self.proj, RowParallelLinear)
+                and isinstance(self.fc1, ColumnParallelLinear)
+                and isinstance(self.fc2, RowParallelLinear)
+                and self.proj.bias.dtype == self.fc1.bias.dtype
+                == self.fc2.bias.dtype == x.dtype):
+            return self._forward_fused(x, tp_group)
 
         residual = x
         y = self.ln_attn(x)

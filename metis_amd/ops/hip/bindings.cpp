@@ -8,6 +8,15 @@ std::vector<torch::Tensor> layernorm_fwd(
 std::vector<torch::Tensor> layernorm_bwd(
     torch::Tensor dy, torch::Tensor x, torch::Tensor gamma,
     torch::Tensor mean, torch::Tensor rstd);
+std::vector<torch::Tensor> bias_residual_layernorm_fwd(
+    torch::Tensor y, torch::Tensor bias, torch::Tensor residual,
+    torch::Tensor gamma, torch::Tensor beta, double eps);
+torch::Tensor bias_residual_add(
+    torch::Tensor y, torch::Tensor bias, torch::Tensor residual);
+std::vector<torch::Tensor> layernorm_bwd_add(
+    torch::Tensor dy, torch::Tensor dres, torch::Tensor x, torch::Tensor gamma,
+    torch::Tensor mean, torch::Tensor rstd, bool want_colsum);
+std::vector<torch::Tensor> gelu_tanh_bwd_bgrad(torch::Tensor h, torch::Tensor da);
 void adamw_step(
     torch::Tensor master, torch::Tensor model, torch::Tensor grad,
     torch::Tensor m, torch::Tensor v,
@@ -90,6 +99,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "fused LayerNorm forward (bf16, fp32 stats)");
     m.def("layernorm_bwd", &layernorm_bwd,
           "fused LayerNorm backward (dx + dgamma/dbeta)");
+    m.def("bias_residual_layernorm_fwd", &bias_residual_layernorm_fwd,
+          "x = residual + (y + bias) with both bf16 roundings, then "
+          "LayerNorm(x) -> (x, z, mean, rstd)");
+    m.def("bias_residual_add", &bias_residual_add,
+          "x = residual + (y + bias) with both bf16 roundings");
+    m.def("layernorm_bwd_add", &layernorm_bwd_add,
+          "LayerNorm backward with a residual gradient folded in -> "
+          "(g = dres + dx, dgamma, dbeta, colsum of g in fp32 or empty)");
+    m.def("gelu_tanh_bwd_bgrad", &gelu_tanh_bwd_bgrad,
+          "tanh-GeLU backward -> (dh bf16, dbias = column sums of dh, fp32)");
     m.def("adamw_step", &adamw_step, "fused AdamW step");
     m.def("attn_fwd", &attn_fwd,
           "flash attention forward (causal, GQA) -> (O, LSE)");

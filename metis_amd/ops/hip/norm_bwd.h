@@ -16,6 +16,13 @@
 //    <= 1024) that grid-stride over row groups, each leaving one
 //    dgamma/dbeta slab; norm_bwd_reduce_kernel sums the slabs in a fixed
 //    order, so the result is deterministic (no atomics).
+//
+// ADD (LayerNorm only) folds the gradient of a residual branch in: with one
+// more input dres [rows, H] the kernel writes g = bf16(dres + bf16(dx)), the
+// sum autograd would form from the two rounded tensors, and keeps a third
+// set of 8 accumulators for the column sums of the rounded g, which is the
+// bias gradient of the linear layer in front of the residual add. Neither
+// costs a pass of its own. ADD = false is the kernel without any of it.
 #pragma once
 
 #include <ATen/hip/HIPContext.h>
@@ -69,7 +76,7 @@ inline void check_args(const torch::Tensor& dy, const torch::Tensor& x,
 //   dx = rstd * (dy*g - mean(dy*g) - xhat * mean(dy*g*xhat)), dgamma, dbeta.
 // RMS = true:  RMSNorm, xhat = x * rstd,
 //   dx = rstd * dy*g - rstd * xhat * mean(dy*g*xhat), dgamma only.
-template <bool RMS, int R, int MAXT>
+template <bool RMS, int R, int MAXT, bool ADD = false>
 __global__ void __launch_bounds__(MAXT) norm_bwd_kernel(
     const bf16x8* __restrict__ dy,
     const bf16x8* __restrict__ x,
@@ -80,7 +87,10 @@ __global__ void __launch_bounds__(MAXT) norm_bwd_kernel(
     float* __restrict__ dgamma_part,      // [gridDim.x, H]
     float* __restrict__ dbeta_part,       // [gridDim.x, H], unused when RMS
     int rows,
-    int hv) {                             // H / VEC
+    int hv,                               // H / VEC
+    const bf16x8* __restrict__ dres,      // ADD only
+    float* __restrict__ colsum_part) {    // [gridDim.x, H], ADD only
+    static_assert(!(RMS && ADD), "ADD is instantiated for LayerNorm only");
     constexpr int NS = RMS ? 1 : 2;       // row sums per row
     __shared__ float red[2][MAX_WAVES][R * NS];
 
@@ -92,7 +102,7 @@ __global__ void __launch_bounds__(MAXT) norm_bwd_kernel(
     const bool live = (int)threadIdx.x < hv;
     const int ci = live ? (int)threadIdx.x : hv - 1;
 
-    float g[VEC], dg[VEC], db[VEC];
+    float g[VEC], dg[VEC], db[VEC], cs[ADD ? VEC : 1];
     {
         const floatx4 g0 = gamma[ci * 2], g1 = gamma[ci * 2 + 1];
         #pragma unroll
@@ -102,13 +112,15 @@ __global__ void __launch_bounds__(MAXT) norm_bwd_kernel(
         }
         #pragma unroll
         for (int k = 0; k < VEC; ++k) dg[k] = db[k] = 0.f;
+        #pragma unroll
+        for (int k = 0; k < (ADD ? VEC : 1); ++k) cs[k] = 0.f;
     }
     const float inv_n = 1.f / (hv * VEC);
     const bf16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
 
     int buf = 0;
     for (long r0 = (long)blockIdx.x * R; r0 < rows; r0 += (long)gridDim.x * R) {
-        bf16x8 dv[R], xv[R];
+        bf16x8 dv[R], xv[R], av[ADD ? R : 1];
         float mu[R], rs[R];
         bool ok[R];
         #pragma unroll
@@ -118,6 +130,7 @@ __global__ void __launch_bounds__(MAXT) norm_bwd_kernel(
             ok[r] = live && (r0 + r < rows);
             dv[r] = dy[row * hv + ci];
             xv[r] = x[row * hv + ci];
+            if (ADD) av[r] = dres[row * hv + ci];
             rs[r] = rstd_in[row];
             mu[r] = RMS ? 0.f : mean_in[row];
         }
@@ -172,6 +185,14 @@ __global__ void __launch_bounds__(MAXT) norm_bwd_kernel(
                 const float v = RMS ? rs[r] * (dyf * g[k]) - rs[r] * xhat * s2
                                     : rs[r] * (dyf * g[k] - s1 - xhat * s2);
                 o[k] = float_to_bf16_bits(v);
+                if (ADD) {
+                    // the sum of the two rounded tensors, rounded; its
+                    // column sum takes the rounded value (dead rows and
+                    // lanes add nothing)
+                    o[k] = float_to_bf16_bits(bf16_bits_to_float(av[r][k])
+                                              + bf16_bits_to_float(o[k]));
+                    cs[k] += ok[r] ? bf16_bits_to_float(o[k]) : 0.f;
+                }
             }
             if (ok[r]) dx[(r0 + r) * hv + ci] = o;
         }
@@ -187,37 +208,46 @@ __global__ void __launch_bounds__(MAXT) norm_bwd_kernel(
             bp[base] = floatx4{db[0], db[1], db[2], db[3]};
             bp[base + 1] = floatx4{db[4], db[5], db[6], db[7]};
         }
+        if (ADD) {
+            floatx4* cp = reinterpret_cast<floatx4*>(colsum_part);
+            cp[base] = floatx4{cs[0], cs[1], cs[2], cs[3]};
+            cp[base + 1] = floatx4{cs[4], cs[5], cs[6], cs[7]};
+        }
     }
 }
 
-// Sum the slabs into dgamma (and dbeta). A workgroup owns 16 columns and
+// Sum the slabs into dgamma (and dbeta, and with THIRD a third array, each
+// in the same order). A workgroup owns 16 columns and
 // spreads the slabs over 64 lanes of them, so every load of a thread is
 // independent; the 64 partials of a column are then added in a fixed order
 // (shuffle over the 4 in a wave, then 16 waves through LDS).
 constexpr int RED_COLS = 16;
 constexpr int RED_THREADS = 1024;
 
-template <bool RMS>
+template <bool RMS, bool THIRD = false>
 __global__ void __launch_bounds__(RED_THREADS) norm_bwd_reduce_kernel(
     const float* __restrict__ dgamma_part,
     const float* __restrict__ dbeta_part,
     float* __restrict__ dgamma,
     float* __restrict__ dbeta,
     int nslabs,
-    int H) {
+    int H,
+    const float* __restrict__ third_part,   // THIRD only
+    float* __restrict__ third) {
     constexpr int SL = RED_THREADS / RED_COLS;          // 64 slab lanes
     constexpr int NWAVE = RED_THREADS / WAVE_SIZE;      // 16
-    __shared__ float red[2][NWAVE][RED_COLS];
+    __shared__ float red[THIRD ? 3 : 2][NWAVE][RED_COLS];
 
     const int cx = threadIdx.x % RED_COLS;
     const int sy = threadIdx.x / RED_COLS;
     const int col = blockIdx.x * RED_COLS + cx;
-    float g = 0.f, b = 0.f;
+    float g = 0.f, b = 0.f, c = 0.f;
     if (col < H) {
         #pragma unroll 4
         for (int s = sy; s < nslabs; s += SL) {
             g += dgamma_part[(long)s * H + col];
             if (!RMS) b += dbeta_part[(long)s * H + col];
+            if (THIRD) c += third_part[(long)s * H + col];
         }
     }
     g += __shfl_xor(g, 16, WAVE_SIZE);
@@ -226,33 +256,42 @@ __global__ void __launch_bounds__(RED_THREADS) norm_bwd_reduce_kernel(
         b += __shfl_xor(b, 16, WAVE_SIZE);
         b += __shfl_xor(b, 32, WAVE_SIZE);
     }
+    if (THIRD) {
+        c += __shfl_xor(c, 16, WAVE_SIZE);
+        c += __shfl_xor(c, 32, WAVE_SIZE);
+    }
     const int lane = threadIdx.x & (WAVE_SIZE - 1);
     const int wave = threadIdx.x / WAVE_SIZE;
     if (lane < RED_COLS) {
         red[0][wave][cx] = g;
         if (!RMS) red[1][wave][cx] = b;
+        if (THIRD) red[2][wave][cx] = c;
     }
     __syncthreads();
     if (threadIdx.x < RED_COLS && col < H) {
         g = 0.f;
         b = 0.f;
+        c = 0.f;
         #pragma unroll
         for (int w = 0; w < NWAVE; ++w) {
             g += red[0][w][cx];
             if (!RMS) b += red[1][w][cx];
+            if (THIRD) c += red[2][w][cx];
         }
         dgamma[col] = g;
         if (!RMS) dbeta[col] = b;
+        if (THIRD) third[col] = c;
     }
 }
 
-template <bool RMS>
+template <bool RMS, bool THIRD = false>
 void launch_reduce(const float* dgamma_part, const float* dbeta_part,
                    float* dgamma, float* dbeta, int nslabs, int H,
-                   hipStream_t stream) {
-    hipLaunchKernelGGL(norm_bwd_reduce_kernel<RMS>,
+                   hipStream_t stream, const float* third_part = nullptr,
+                   float* third = nullptr) {
+    hipLaunchKernelGGL((norm_bwd_reduce_kernel<RMS, THIRD>),
         dim3((H + RED_COLS - 1) / RED_COLS), dim3(RED_THREADS), 0, stream,
-        dgamma_part, dbeta_part, dgamma, dbeta, nslabs, H);
+        dgamma_part, dbeta_part, dgamma, dbeta, nslabs, H, third_part, third);
 }
 
 // Rows per iteration. 4 rows cost ~136 VGPRs = 3 waves/SIMD = 12 waves/CU;
@@ -298,20 +337,23 @@ int grid_for(long rows, long H) {
 }
 
 // dx plus `grid` slabs ([grid, H] floats each in dgamma_part/dbeta_part).
-template <bool RMS>
+// ADD: g = dres + dx in dx's place and a third slab array colsum_part.
+template <bool RMS, bool ADD = false>
 void launch_main(const void* dy, const void* x, const float* gamma,
                  const float* mean, const float* rstd, void* dx,
                  float* dgamma_part, float* dbeta_part,
-                 long rows, long H, int grid, hipStream_t stream) {
+                 long rows, long H, int grid, hipStream_t stream,
+                 const void* dres = nullptr, float* colsum_part = nullptr) {
     const int threads = block_threads(H);
     #define NORM_BWD_LAUNCH(RR, MT)                                            \
-        hipLaunchKernelGGL((norm_bwd_kernel<RMS, RR, MT>), dim3(grid),         \
+        hipLaunchKernelGGL((norm_bwd_kernel<RMS, RR, MT, ADD>), dim3(grid),    \
             dim3(threads), 0, stream,                                          \
             reinterpret_cast<const bf16x8*>(dy),                               \
             reinterpret_cast<const bf16x8*>(x),                                \
             reinterpret_cast<const floatx4*>(gamma), mean, rstd,               \
             reinterpret_cast<bf16x8*>(dx), dgamma_part, dbeta_part,            \
-            (int)rows, (int)(H / VEC))
+            (int)rows, (int)(H / VEC),                                         \
+            reinterpret_cast<const bf16x8*>(dres), colsum_part)
     if (threads <= R4_MAX_THREADS) NORM_BWD_LAUNCH(4, R4_MAX_THREADS);
     else NORM_BWD_LAUNCH(2, 1024);
     #undef NORM_BWD_LAUNCH

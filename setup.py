@@ -20,6 +20,7 @@ HIP_DIR = os.path.join(ROOT, "metis_amd", "ops", "hip")
 sources = [
     os.path.join(HIP_DIR, "bindings.cpp"),
     os.path.join(HIP_DIR, "layernorm.hip"),
+    os.path.join(HIP_DIR, "gelu.hip"),
     os.path.join(HIP_DIR, "adamw.hip"),
     os.path.join(HIP_DIR, "attention.hip"),
     os.path.join(HIP_DIR, "attention_bwd.hip"),
