@@ -11,18 +11,20 @@
 //     global into registers; opposing-side tiles are 64 rows, staged into
 //     LDS as NATURAL padded images (K, V for dQ; Q, dO for dKV) with the
 //     T14 split: the next tile's chunks load to registers under the
-//     current tile's compute. The same image feeds the plain B-fragment
-//     reads (QK^T, dO V^T) and the ds_read_b64_tr_b16 B-fragments (dS K;
-//     dS^T Q, P^T dO) — no transposed copy exists;
-//   * dS / P^T redistribute through per-wave LDS (raw bf16 bits as
-//     shorts), published by a wave-local compiler fence — DS ops of one
-//     wave complete in order;
+//     current tile's compute. The same image feeds the plain A-fragment
+//     reads of the first products and the ds_read_b64_tr_b16 B-fragments
+//     of the second (dS K; dS^T Q, P^T dO) — no transposed copy exists;
+//   * P and dS never leave the registers: the first products are oriented
+//     with the OPPOSING-side row in the accumulator registers and the
+//     own-side row on the lane, so their accumulators are the A operand of
+//     the second products as they stand (attn_tile.h AccFrag), the tr16
+//     reads following the accumulator's k order;
 //   * D in {64, 80, 96, 128} template instantiations (register arrays
 //     compile-time indexed).
 //
-//   dQ kernel:  P = exp(scale*QK^T - lse); dP = dO V^T;
-//               dS = scale * P o (dP - delta); dQ += dS @ K
-//   dKV kernel: P^T = exp(scale*K Q^T - lse[col]); dP^T = V dO^T;
+//   dQ kernel:  P^T = exp(scale*K Q^T - lse[col]); dP^T = V dO^T;
+//               dS^T = scale * P^T o (dP^T - delta[col]); dQ += dS @ K
+//   dKV kernel: P = exp(scale*Q K^T - lse[row]); dP = dO V^T;
 //               dV += P^T @ dO; dK += dS^T @ Q
 
 #include <torch/extension.h>
@@ -38,7 +40,6 @@ using namespace attn_tile;
 constexpr int THREADS = 256;
 constexpr int RBLK = 128;    // dQ: q rows per block (2 x 16 per wave)
 constexpr int CTILE = 64;    // opposing-side tile rows
-constexpr int VROW = CTILE + VPAD;   // per-wave dS / P^T tile row length
 // Waves/SIMD asked of __launch_bounds__ = blocks/CU the LDS is sized for (the
 // eight-wave D=64 dKV block reaches 4 waves/SIMD, so two of it fit as well).
 constexpr int RESIDENT = 2;
@@ -48,30 +49,43 @@ static_assert(RBLK == ATTN_SEQ_TILE, "check_attn_qkv pins S to this tile");
 template <int D>
 constexpr int dkv_rows() { return D == 64 ? 128 : 64; }
 
-// LDS. dQ: K and V images, dS tiles [4 waves][2 row blocks][16][VROW];
-// dKV: Q and dO images, dS^T tiles [NW][16][VROW] then P^T tiles likewise.
+// Waves/SIMD each kernel is compiled for (the register budget it may not
+// exceed); the LDS leaves room for more blocks than that at every D.
 template <int D>
-using DqLayout = TileLayout<D, CTILE, THREADS / 64 * 2, RESIDENT>;
+constexpr int dq_waves() { return D == 64 ? 3 : 2; }
 template <int D>
-using DkvLayout = TileLayout<D, CTILE, 2 * (dkv_rows<D>() / 16), RESIDENT>;
-static_assert(DqLayout<64>::bytes == 36864 && DqLayout<80>::bytes == 40960
-              && DqLayout<96>::bytes == 45056 && DqLayout<128>::bytes == 53248);
-static_assert(DkvLayout<64>::bytes == 55296 && DkvLayout<80>::bytes == 40960
-              && DkvLayout<96>::bytes == 45056 && DkvLayout<128>::bytes == 53248);
+constexpr int dkv_waves() { return D == 64 ? 4 : D == 80 ? 3 : 2; }
+
+// dQ: whether the two row blocks of a wave run through a tile together,
+// each K and V fragment read from LDS once for both, or one after the other
+// (the same arithmetic per row block either way, so the choice is invisible
+// in the results). Together takes about 45 more VGPRs: scratch at D = 64
+// and 128, and at D = 80 the packed kernel's third wave per SIMD, without
+// which it measured 2 % slower; it wins only at D = 96 (BENCHMARKS.md).
+template <int D>
+constexpr bool dq_pair_rows() { return D == 96; }
+
+// LDS. dQ: K and V images; dKV: Q and dO images. Nothing else.
+template <int D>
+using DqLayout = TileLayout<D, CTILE, 0, RESIDENT>;
+template <int D>
+using DkvLayout = TileLayout<D, CTILE, 0, RESIDENT>;
+static_assert(DqLayout<64>::bytes == 18432 && DqLayout<80>::bytes == 22528
+              && DqLayout<96>::bytes == 26624 && DqLayout<128>::bytes == 34816);
 
 // ---------------------------------------------------------------- dQ ----
 // PACKED (attn_tile.h BlockCoord) in both kernels: Q, K, V and dQ / dK, dV
 // point at the q, k, v column blocks of qkv and dqkv [B, S, (H + 2 Hkv) * D];
 // dO is [B, S, H * D]; LSE and Delta stay [B, H, S].
 template <int D, bool PACKED>
-__global__ __launch_bounds__(THREADS, RESIDENT) void attn_bwd_dq_kernel(
+__global__ __launch_bounds__(THREADS, dq_waves<D>()) void attn_bwd_dq_kernel(
     const bf16* __restrict__ Q, const bf16* __restrict__ K,
     const bf16* __restrict__ V, const bf16* __restrict__ dO,
     const float* __restrict__ LSE, const float* __restrict__ Delta,
     bf16* __restrict__ dQ,
     int B, int H, int Hkv, int S, float scale) {
     const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int col16 = lane & 15;
     const int k8 = lane >> 4;
 
@@ -90,19 +104,18 @@ __global__ __launch_bounds__(THREADS, RESIDENT) void attn_bwd_dq_kernel(
     extern __shared__ __attribute__((aligned(16))) char smem[];
     short* Ks = reinterpret_cast<short*>(smem) + L::a_off;
     short* Vs = reinterpret_cast<short*>(smem) + L::b_off;
-    short* Sw = reinterpret_cast<short*>(smem) + L::w_off + wave * 2 * L::w_tile;
 
-    // per-row state and Q/dO fragments for both row blocks
-    float lse_r[2][4], delta_r[2][4];
+    // Q/dO fragments for both row blocks: the B operands of S^T = K Q^T and
+    // dP^T = V dO^T, [k = d][n = q row on the lane]. The lane's q row is
+    // q0 + col16 in every first-product accumulator, so it needs one
+    // lse/delta pair per row block.
+    float lse_c[2], delta_c[2];
     bf16x8 q_frag[2][dchunks], do_frag[2][dchunks];
     #pragma unroll
     for (int rb = 0; rb < 2; ++rb) {
         const int q0 = qb + rbid[rb] * 16;
-        #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            lse_r[rb][r] = LSE[row_base + q0 + k8 * 4 + r];
-            delta_r[rb][r] = Delta[row_base + q0 + k8 * 4 + r];
-        }
+        lse_c[rb] = LSE[row_base + q0 + col16];
+        delta_c[rb] = Delta[row_base + q0 + col16];
         #pragma unroll
         for (int c = 0; c < dchunks; ++c) {
             q_frag[rb][c] = frag8<D>(Q + q_base, q0 + col16, c * 32 + k8 * 8,
@@ -114,7 +127,7 @@ __global__ __launch_bounds__(THREADS, RESIDENT) void attn_bwd_dq_kernel(
 
     floatx4 dq_acc[2][djtiles] = {};
 
-    // T14 staged K (one natural image serves the QK^T reads and the tr16
+    // T14 staged K (one natural image serves the S^T reads and the tr16
     // reads of dS K); V has no stage registers and is loaded when its
     // natural image is written. Lanes walk kv rows for both; in PACKED
     // mode, where a row is its own 2*D-byte run, whole rows (dKV likewise).
@@ -124,6 +137,65 @@ __global__ __launch_bounds__(THREADS, RESIDENT) void attn_bwd_dq_kernel(
     const bf16* Kh = K + bc.kv_base;
     const bf16* Vh = V + bc.kv_base;
 
+    // One KV tile for the row blocks rb >= RB0 (the later block is live in
+    // every tile of the loop, the earlier one is not). Each K and V
+    // fragment is read once and feeds both row blocks.
+    auto tile_body = [&](auto rb_lo, auto rb_hi, int kv0) {
+        constexpr int RB0 = decltype(rb_lo)::value, RB1 = decltype(rb_hi)::value;
+
+        AccFrag ds_frag[2][CTILE / 32];   // dS^T tiles, [kv rows][q on the lane]
+        __builtin_amdgcn_s_setprio(1);
+        #pragma unroll
+        for (int j = 0; j < CTILE / 16; ++j) {
+            floatx4 st_acc[2] = {}, dpt_acc[2] = {};
+            #pragma unroll
+            for (int c = 0; c < dchunks; ++c) {
+                bf16x8 kf, vf;
+                lds_frag2<D, KSLOT>(Ks, Vs, j * 16 + col16, c * 32 + k8 * 8,
+                                    kf, vf);
+                #pragma unroll
+                for (int rb = RB0; rb < RB1; ++rb) {
+                    st_acc[rb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                        kf, q_frag[rb][c], st_acc[rb], 0, 0, 0);
+                    dpt_acc[rb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                        vf, do_frag[rb][c], dpt_acc[rb], 0, 0, 0);
+                }
+            }
+            #pragma unroll
+            for (int rb = RB0; rb < RB1; ++rb) {
+                const int qrow = qb + rbid[rb] * 16 + col16;
+                floatx4 ds;
+                #pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int kvrow = kv0 + j * 16 + k8 * 4 + r;
+                    const float p =
+                        (kvrow > qrow)
+                            ? 0.f
+                            : __expf(st_acc[rb][r] * scale - lse_c[rb]);
+                    ds[r] = scale * p * (dpt_acc[rb][r] - delta_c[rb]);
+                }
+                ds_frag[rb][j >> 1].set_half(j & 1, ds);
+            }
+        }
+        __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_sched_barrier(0);
+
+        // dQ += dS K: dS is the A operand from the registers, K the tr16
+        // B-fragment in the accumulator's k order
+        #pragma unroll
+        for (int ks = 0; ks < CTILE / 32; ++ks) {
+            #pragma unroll
+            for (int jd = 0; jd < djtiles; ++jd) {
+                const bf16x8 kt_frag = tr16_frag_acc<KSLOT>(
+                    Ks, ks * 32, k8, jd * 16, col16);
+                #pragma unroll
+                for (int rb = RB0; rb < RB1; ++rb)
+                    dq_acc[rb][jd] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                        ds_frag[rb][ks].frag(), kt_frag, dq_acc[rb][jd], 0, 0, 0);
+            }
+        }
+    };
+
     const int kv_end = qb + RBLK;
     stage.issue_loads(Kh, Vh, 0, pitch, pitch);
     for (int kv0 = 0; kv0 < kv_end; kv0 += CTILE) {
@@ -132,68 +204,17 @@ __global__ __launch_bounds__(THREADS, RESIDENT) void attn_bwd_dq_kernel(
             stage.issue_loads(Kh, Vh, kv0 + CTILE, pitch, pitch);
         __syncthreads();
 
-        bool rb_active[2];
-        #pragma unroll
-        for (int rb = 0; rb < 2; ++rb) {
-            const int q0 = qb + rbid[rb] * 16;
-            rb_active[rb] = kv0 <= q0 + 15;
-            if (!rb_active[rb]) continue;
-
-            __builtin_amdgcn_s_setprio(1);
-            floatx4 s_acc[4], dp_acc[4];
-            #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                s_acc[j] = floatx4{0.f, 0.f, 0.f, 0.f};
-                dp_acc[j] = floatx4{0.f, 0.f, 0.f, 0.f};
-                const int kvrow = j * 16 + col16;
-                #pragma unroll
-                for (int c = 0; c < dchunks; ++c) {
-                    const int d0 = c * 32 + k8 * 8;
-                    bf16x8 kf, vf;
-                    lds_frag2<D, KSLOT>(Ks, Vs, kvrow, d0, kf, vf);
-                    s_acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                        q_frag[rb][c], kf, s_acc[j], 0, 0, 0);
-                    dp_acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                        do_frag[rb][c], vf, dp_acc[j], 0, 0, 0);
-                }
-            }
-            __builtin_amdgcn_s_setprio(0);
-
-            short* Srb = Sw + rb * 16 * VROW;
-            #pragma unroll
-            for (int j = 0; j < 4; ++j)
-                #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int qrow = q0 + k8 * 4 + r;
-                    const int kvcol = kv0 + j * 16 + col16;
-                    float p = (kvcol > qrow)
-                                  ? 0.f
-                                  : __expf(s_acc[j][r] * scale - lse_r[rb][r]);
-                    float ds = scale * p * (dp_acc[j][r] - delta_r[rb][r]);
-                    Srb[(k8 * 4 + r) * VROW + j * 16 + col16] =
-                        float_to_bf16_bits(ds);
-                }
-        }
-
-        // wave-local publish of dS (DS ops of one wave are in order)
-        asm volatile("" ::: "memory");
-
-        #pragma unroll
-        for (int rb = 0; rb < 2; ++rb) {
-            if (!rb_active[rb]) continue;
-            const short* Srb = Sw + rb * 16 * VROW;
-            #pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                bf16x8 ds_frag = *reinterpret_cast<const bf16x8*>(
-                    Srb + col16 * VROW + ks * 32 + k8 * 8);
-                #pragma unroll
-                for (int jd = 0; jd < djtiles; ++jd) {
-                    bf16x8 kt_frag = tr16_frag<KSLOT>(
-                        Ks, ks * 32 + k8 * 8, jd * 16, col16);
-                    dq_acc[rb][jd] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                        ds_frag, kt_frag, dq_acc[rb][jd], 0, 0, 0);
-                }
-            }
+        // a row block is live while the tile starts at or below its diagonal
+        const bool early_live = kv0 <= qb + rbid[0] * 16 + 15;
+        constexpr std::integral_constant<int, 0> i0;
+        constexpr std::integral_constant<int, 1> i1;
+        constexpr std::integral_constant<int, 2> i2;
+        if constexpr (dq_pair_rows<D>()) {
+            if (early_live) tile_body(i0, i2, kv0);
+            else tile_body(i1, i2, kv0);
+        } else {
+            if (early_live) tile_body(i0, i1, kv0);
+            tile_body(i1, i2, kv0);
         }
         __syncthreads();
     }
@@ -219,7 +240,7 @@ __global__ __launch_bounds__(THREADS, RESIDENT) void attn_bwd_dq_kernel(
 // VGPR footprints lose the second independent block's latency
 // cover), so those stay 4-wave x 64 rows.
 template <int D, bool PACKED>
-__global__ __launch_bounds__(dkv_rows<D>() / 16 * 64, RESIDENT)
+__global__ __launch_bounds__(dkv_rows<D>() / 16 * 64, dkv_waves<D>())
 void attn_bwd_dkv_kernel(
     const bf16* __restrict__ Q, const bf16* __restrict__ K,
     const bf16* __restrict__ V, const bf16* __restrict__ dO,
@@ -228,7 +249,7 @@ void attn_bwd_dkv_kernel(
     bf16* __restrict__ dV,
     int B, int H, int Hkv, int S, float scale) {
     const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int col16 = lane & 15;
     const int k8 = lane >> 4;
 
@@ -250,10 +271,9 @@ void attn_bwd_dkv_kernel(
     extern __shared__ __attribute__((aligned(16))) char smem[];
     short* Qs = reinterpret_cast<short*>(smem) + L::a_off;
     short* dOs = reinterpret_cast<short*>(smem) + L::b_off;
-    short* Sw = reinterpret_cast<short*>(smem) + L::w_off + wave * L::w_tile;
-    short* Pw = reinterpret_cast<short*>(smem) + L::w_off + (NW + wave) * L::w_tile;
 
-    // K and V fragments for this wave's rows (A layout, m = col16)
+    // K and V fragments for this wave's rows: the B operands of S = Q K^T
+    // and dP = dO V^T, [k = d][n = kv row on the lane]
     bf16x8 k_frag[dchunks], v_frag[dchunks];
     #pragma unroll
     for (int c = 0; c < dchunks; ++c) {
@@ -276,70 +296,86 @@ void attn_bwd_dkv_kernel(
     const int q_start = bc.tile * KVB;   // causal: from the block's kv start
     stage.issue_loads(Qh, dOh, q_start, pitch, bc.o_pitch);
     for (int q0 = q_start; q0 < S; q0 += CTILE) {
+        // The first-product accumulators hold q rows 16 j + 4 k8 + r in their
+        // registers: one aligned float4 of LSE and of Delta per subtile j.
+        // A tile runs as two 32-row halves, each the k range of one second
+        // product. The first half's rows are loaded here, ahead of the LDS
+        // write, the barrier and the MFMAs and behind the staged tile in the
+        // load queue; the second half's under the first half's second products.
+        const bool active = q0 + CTILE - 1 >= kv0;
+        float4 lse4[2], delta4[2];
+        auto load_rows = [&](int ks) {
+            #pragma unroll
+            for (int jj = 0; jj < 2; ++jj) {
+                const long q = row_base + q0 + ks * 32 + jj * 16 + k8 * 4;
+                lse4[jj] = *reinterpret_cast<const float4*>(LSE + q);
+                delta4[jj] = *reinterpret_cast<const float4*>(Delta + q);
+            }
+        };
+        if (active) load_rows(0);
+
         stage.write_stage(Qs, dOs, dOh, q0, bc.o_pitch);
         if (q0 + CTILE < S)
             stage.issue_loads(Qh, dOh, q0 + CTILE, pitch, bc.o_pitch);
         __syncthreads();
 
-        const bool active = q0 + CTILE - 1 >= kv0;
         if (active) {
-            __builtin_amdgcn_s_setprio(1);
-            floatx4 st_acc[4], dpt_acc[4];
             #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                st_acc[j] = floatx4{0.f, 0.f, 0.f, 0.f};
-                dpt_acc[j] = floatx4{0.f, 0.f, 0.f, 0.f};
-                const int qrow = j * 16 + col16;
+            for (int ks = 0; ks < CTILE / 32; ++ks) {
+                AccFrag p_frag, ds_frag;   // [32 q rows][kv on the lane]
+                __builtin_amdgcn_s_setprio(1);
                 #pragma unroll
-                for (int c = 0; c < dchunks; ++c) {
-                    const int d0 = c * 32 + k8 * 8;
-                    bf16x8 qf, dof;
-                    lds_frag2<D, KSLOT>(Qs, dOs, qrow, d0, qf, dof);
-                    st_acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                        k_frag[c], qf, st_acc[j], 0, 0, 0);
-                    dpt_acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                        v_frag[c], dof, dpt_acc[j], 0, 0, 0);
+                for (int jj = 0; jj < 2; ++jj) {
+                    const int j = ks * 2 + jj;
+                    floatx4 s_acc = {}, dp_acc = {};
+                    #pragma unroll
+                    for (int c = 0; c < dchunks; ++c) {
+                        bf16x8 qf, dof;
+                        lds_frag2<D, KSLOT>(Qs, dOs, j * 16 + col16,
+                                            c * 32 + k8 * 8, qf, dof);
+                        s_acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                            qf, k_frag[c], s_acc, 0, 0, 0);
+                        dp_acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                            dof, v_frag[c], dp_acc, 0, 0, 0);
+                    }
+                    const float lse_r[4] = {lse4[jj].x, lse4[jj].y, lse4[jj].z,
+                                            lse4[jj].w};
+                    const float delta_r[4] = {delta4[jj].x, delta4[jj].y,
+                                              delta4[jj].z, delta4[jj].w};
+                    floatx4 p, ds;
+                    #pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int qrow = q0 + j * 16 + k8 * 4 + r;
+                        const int kvrow = kv0 + col16;
+                        p[r] = (qrow < kvrow)
+                                   ? 0.f
+                                   : __expf(s_acc[r] * scale - lse_r[r]);
+                        ds[r] = scale * p[r] * (dp_acc[r] - delta_r[r]);
+                    }
+                    p_frag.set_half(jj, p);
+                    ds_frag.set_half(jj, ds);
                 }
-            }
-            __builtin_amdgcn_s_setprio(0);
+                __builtin_amdgcn_s_setprio(0);
+                __builtin_amdgcn_sched_barrier(0);
+                if (ks + 1 < CTILE / 32) load_rows(ks + 1);
 
-            #pragma unroll
-            for (int j = 0; j < 4; ++j)
-                #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int kvrow = kv0 + k8 * 4 + r;
-                    const int qcol = q0 + j * 16 + col16;
-                    float p = (qcol < kvrow)
-                                  ? 0.f
-                                  : __expf(st_acc[j][r] * scale
-                                           - LSE[row_base + qcol]);
-                    float ds = scale * p
-                               * (dpt_acc[j][r] - Delta[row_base + qcol]);
-                    Sw[(k8 * 4 + r) * VROW + j * 16 + col16] =
-                        float_to_bf16_bits(ds);
-                    Pw[(k8 * 4 + r) * VROW + j * 16 + col16] =
-                        float_to_bf16_bits(p);
-                }
-
-            asm volatile("" ::: "memory");   // wave-local publish
-
-            #pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                bf16x8 dst_frag = *reinterpret_cast<const bf16x8*>(
-                    Sw + col16 * VROW + ks * 32 + k8 * 8);
-                bf16x8 pt_frag = *reinterpret_cast<const bf16x8*>(
-                    Pw + col16 * VROW + ks * 32 + k8 * 8);
+                // dK += dS^T Q, dV += P^T dO: the tiles are the A operand
+                // from the registers, Q and dO tr16 B-fragments in the
+                // accumulator's k order
+                const bf16x8 dst_frag = ds_frag.frag();
+                const bf16x8 pt_frag = p_frag.frag();
                 #pragma unroll
                 for (int jd = 0; jd < djtiles; ++jd) {
-                    bf16x8 qt_frag = tr16_frag<KSLOT>(
-                        Qs, ks * 32 + k8 * 8, jd * 16, col16);
+                    bf16x8 qt_frag = tr16_frag_acc<KSLOT>(
+                        Qs, ks * 32, k8, jd * 16, col16);
                     dk_acc[jd] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
                         dst_frag, qt_frag, dk_acc[jd], 0, 0, 0);
-                    bf16x8 dot_frag = tr16_frag<KSLOT>(
-                        dOs, ks * 32 + k8 * 8, jd * 16, col16);
+                    bf16x8 dot_frag = tr16_frag_acc<KSLOT>(
+                        dOs, ks * 32, k8, jd * 16, col16);
                     dv_acc[jd] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
                         pt_frag, dot_frag, dv_acc[jd], 0, 0, 0);
                 }
+                __builtin_amdgcn_sched_barrier(0);
             }
         }
         __syncthreads();
@@ -479,6 +515,8 @@ std::vector<torch::Tensor> attn_bwd(
     auto qc = q.contiguous(), kc = k.contiguous(), vc = v.contiguous();
     auto doc = d_o.contiguous();
     auto lsec = lse.contiguous(), dc = delta.contiguous();
+    check_attn_rows_aligned(lsec, "lse");
+    check_attn_rows_aligned(dc, "delta");
 
     auto dq = torch::empty_like(qc);
     auto dk = torch::empty({a.B, a.H, a.S, a.D}, q.options());

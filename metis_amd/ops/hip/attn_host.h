@@ -92,6 +92,12 @@ inline void check_attn_packed_out(const torch::Tensor& t, const char* name,
                 name, " must be [B, S, H * D]");
 }
 
+// The dKV kernel reads lse and delta four rows (one float4) at a time.
+inline void check_attn_rows_aligned(const torch::Tensor& t, const char* name) {
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0,
+                name, " must be 16-byte aligned");
+}
+
 // lse or delta: fp32 [B, H, S], contiguous, on `like`'s device.
 inline void check_attn_rows(const torch::Tensor& t, const char* name,
                             const torch::Tensor& like, long B, long H, long S) {
@@ -102,6 +108,7 @@ inline void check_attn_rows(const torch::Tensor& t, const char* name,
     TORCH_CHECK(t.dim() == 3 && t.size(0) == B && t.size(1) == H
                 && t.size(2) == S && t.is_contiguous(),
                 name, " must be a contiguous [B, H, S]");
+    check_attn_rows_aligned(t, name);
 }
 
 // f(std::integral_constant<int, N>{}) with N = D.

@@ -73,16 +73,18 @@ __device__ __forceinline__ void lds_frag2(const short* img_a, const short* img_b
     }
 }
 
-// B-fragment via ds_read_b64_tr_b16 from a NATURAL [row][KSLOT*8] LDS
-// image: per 16-lane group, two reads cover the 8 opposing-index rows;
-// lane l&15 receives its d-column (semantics pinned by ext.tr16_probe).
+// Fragment via ds_read_b64_tr_b16 from a NATURAL [row][KSLOT*8] LDS image:
+// per 16-lane group, two reads cover two blocks of 4 opposing-index rows,
+// starting at row_lo (elements 0..3) and row_hi (elements 4..7); lane l&15
+// receives its d-column (semantics pinned by ext.tr16_probe). The caller
+// passes each block's first row FOR ITS LANE GROUP; two row rules are in use.
 template <int KSLOT>
-__device__ __forceinline__ bf16x8 tr16_frag(
-    const short* img, int row0, int col0, int p4) {
+__device__ __forceinline__ bf16x8 tr16_rows(
+    const short* img, int row_lo, int row_hi, int col0, int p4) {
     bf16x8 out;
     #pragma unroll
     for (int r = 0; r < 2; ++r) {
-        const int row = row0 + 4 * r + (p4 >> 2);
+        const int row = (r ? row_hi : row_lo) + (p4 >> 2);
         const int col = col0 + (p4 & 3) * 4;
         short4v t = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
             (__attribute__((address_space(3))) short4v*)(
@@ -94,6 +96,56 @@ __device__ __forceinline__ bf16x8 tr16_frag(
     }
     return out;
 }
+
+// Natural k order: element i of lane group g is row row0 + i of the image,
+// row0 = chunk + 8g. The B operand [k][n = d] against an A operand read
+// in natural order (lds_frag / frag8).
+template <int KSLOT>
+__device__ __forceinline__ bf16x8 tr16_frag(
+    const short* img, int row0, int col0, int p4) {
+    return tr16_rows<KSLOT>(img, row0, row0 + 4, col0, p4);
+}
+
+// Accumulator k order: the other operand of the product is acc_frag() of
+// the two 16-row accumulator tiles that start at rows `chunk` and
+// `chunk + 16`, so element i of lane group g is row chunk + 16 (i >> 2) +
+// 4g + (i & 3). B operand [k][n = d] or, the read being symmetric, the A
+// operand [m = d][k] of the transposed product.
+template <int KSLOT>
+__device__ __forceinline__ bf16x8 tr16_frag_acc(
+    const short* img, int chunk, int g, int col0, int p4) {
+    return tr16_rows<KSLOT>(img, chunk + 4 * g, chunk + 16 + 4 * g, col0, p4);
+}
+
+// Two fp32 values to packed bf16 bits, round-to-nearest-even
+// (v_cvt_pk_bf16_f32), `lo` in the low half.
+__device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {
+    typedef float floatx2 __attribute__((ext_vector_type(2)));
+    typedef __bf16 bf16x2v __attribute__((ext_vector_type(2)));
+    return __builtin_bit_cast(
+        unsigned, __builtin_convertvector(floatx2{lo, hi}, bf16x2v));
+}
+
+// An MFMA accumulator tile as the next MFMA's operand, no LDS and no lane
+// movement. Lane (c = l & 15, g = l >> 4) holds X[4g + r][c] of a 16x16
+// accumulator tile X. Two tiles (the rows `chunk ..` and `chunk + 16 ..` of
+// one 32-row strip) give the 8-element fragment of a product that sums over
+// X's ROW index: elements 0..3 from x_lo, 4..7 from x_hi. As the B operand
+// that is X, as the A operand X^T. The k order inside the 32-row strip is
+// the permuted one of tr16_frag_acc, which the other operand must follow.
+// A half is one tile's four values; a kernel that finishes its tiles one at
+// a time fills the halves as they come.
+struct AccFrag {
+    unsigned w[4];
+    __device__ __forceinline__ void set_half(int hi, floatx4 x) {
+        w[2 * hi + 0] = pack_bf16x2(x[0], x[1]);
+        w[2 * hi + 1] = pack_bf16x2(x[2], x[3]);
+    }
+    __device__ __forceinline__ bf16x8 frag() const {
+        typedef unsigned uintx4 __attribute__((ext_vector_type(4)));
+        return __builtin_bit_cast(bf16x8, uintx4{w[0], w[1], w[2], w[3]});
+    }
+};
 
 // blockIdx.x = (batch * H + head) * tiles + tile: the tile index, the
 // offsets of row 0 of that q head and of its GQA kv head, and the distance
