@@ -27,6 +27,7 @@ from metis_amd.ops import LayerNorm
 from metis_amd.ops import residual as _res
 from metis_amd.ops.attention import decode_attention, packed_flash_attention
 from metis_amd.ops.cross_entropy import cross_entropy
+from metis_amd.ops.linear import linear
 from metis_amd.ops.mlp import fused_mlp
 from metis_amd.ops.relayout import heads_merge, qkv_split_transpose
 from metis_amd.partial_grads import mark_partial
@@ -294,7 +295,7 @@ class ColumnParallelLinear(nn.Module):
 
     def forward(self, x: torch.Tensor, tp_group) -> torch.Tensor:
         x = _CopyToTP.apply(x, tp_group)
-        return F.linear(x, self.weight, self.bias)
+        return linear(x, self.weight, self.bias)
 
 
 class RowParallelLinear(nn.Module):
@@ -309,7 +310,7 @@ class RowParallelLinear(nn.Module):
         _init_linear(self.weight, in_features)
 
     def forward(self, x: torch.Tensor, tp_group) -> torch.Tensor:
-        y = F.linear(x, self.weight)
+        y = linear(x, self.weight)
         y = _ReduceFromTP.apply(y, tp_group)
         return y + self.bias
 
@@ -358,16 +359,16 @@ class GPTBlock(nn.Module):
         attn = packed_flash_attention(
             qkv, self.heads_per_rank, self.heads_per_rank, self.head_dim
         )
-        part = _ReduceFromTP.apply(F.linear(attn, self.proj.weight), tp_group)
+        part = _ReduceFromTP.apply(linear(attn, self.proj.weight), tp_group)
         x, y = _res.bias_residual_layer_norm(
             part, self.proj.bias, x, self.ln_mlp.weight, self.ln_mlp.bias,
             self.ln_mlp.eps)
         # the GEMM adds fc1.bias as before; its gradient comes from the
         # GeLU backward instead of a column reduce over dh
-        h = F.linear(_CopyToTP.apply(y, tp_group), self.fc1.weight,
-                     self.fc1.bias.detach())
+        h = linear(_CopyToTP.apply(y, tp_group), self.fc1.weight,
+                   self.fc1.bias.detach())
         a = _res.gelu_bgrad(h, self.fc1.bias)
-        part = _ReduceFromTP.apply(F.linear(a, self.fc2.weight), tp_group)
+        part = _ReduceFromTP.apply(linear(a, self.fc2.weight), tp_group)
         return _res.bias_residual_add(part, self.fc2.bias, x)
 
     def forward(self, x: torch.Tensor, tp_group, sp: bool = False,

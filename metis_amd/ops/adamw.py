@@ -20,6 +20,7 @@ import torch
 import torch.distributed as dist
 
 from metis_amd import ops as _ops
+from metis_amd.ops import linear as _linear
 
 
 class FusedAdamW:
@@ -145,6 +146,8 @@ class FusedAdamW:
         """Apply one AdamW step. With ``pre_gathered=True`` the caller has
         already filled (and possibly all-reduced) ``grad_flat``."""
         self.step_count += 1
+        # the fused kernel writes the bf16 weights without autograd seeing it
+        _linear.bump_epoch()
         grads = self._grad_flat if pre_gathered else self._gather_grads()
 
         if self._shard_ws > 1:  # ZeRO-1: update the local shard, gather weights
@@ -180,6 +183,7 @@ class FusedAdamW:
         }
 
     def load_state_dict(self, state: dict) -> None:
+        _linear.bump_epoch()
         self.step_count = state["step"]
         self.master.copy_(state["master"])
         self.m.copy_(state["m"])

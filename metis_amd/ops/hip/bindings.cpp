@@ -93,6 +93,16 @@ torch::Tensor qkv_split_transpose_bwd(
 torch::Tensor heads_merge(torch::Tensor x);
 torch::Tensor heads_unmerge(torch::Tensor y, long H);
 torch::Tensor tr16_probe(long stride_elems);
+torch::Tensor lt_linear_dgrad_tn(torch::Tensor dy, torch::Tensor wt);
+torch::Tensor lt_linear_dgrad(torch::Tensor dy, torch::Tensor w, long algo);
+torch::Tensor lt_linear_wgrad(torch::Tensor dy, torch::Tensor x, long algo);
+long lt_version();
+std::vector<long> lt_supported_algos(
+    const std::string& op, long M, long N, long K);
+long lt_heuristic_algo(const std::string& op, long M, long N, long K);
+long lt_wgrad_bgradb_algos(long M, long N, long K);
+torch::Tensor transpose_bf16(torch::Tensor w);
+void transpose_bf16_out(torch::Tensor w, torch::Tensor wt);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("layernorm_fwd", &layernorm_fwd,
@@ -188,6 +198,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "hipblaslt GEMM with GELU_AUX_BIAS epilogue (fc1 fused)");
     m.def("lt_matmul_dgelu_bgrad", &lt_matmul_dgelu_bgrad,
           "hipblaslt GEMM with DGELU_BGRAD epilogue (fc2 data grad fused)");
+    m.def("lt_linear_dgrad_tn", &lt_linear_dgrad_tn,
+          "dx [M,K] = dy [M,N] @ wt [K,N]^T (hipBLASLt TN route)");
+    m.def("lt_linear_dgrad", &lt_linear_dgrad,
+          "dx [M,K] = dy [M,N] @ w [N,K]; algo = solution index or -1");
+    m.def("lt_linear_wgrad", &lt_linear_wgrad,
+          "dw [N,K] = dy [M,N]^T @ x [M,K]; algo = solution index or -1");
+    m.def("lt_version", &lt_version, "hipblasLtGetVersion");
+    m.def("lt_supported_algos", &lt_supported_algos,
+          "supported solution indices for op (dgrad_tn|dgrad|wgrad) at M,N,K");
+    m.def("lt_heuristic_algo", &lt_heuristic_algo,
+          "solution index of the heuristic's first choice");
+    m.def("lt_wgrad_bgradb_algos", &lt_wgrad_bgradb_algos,
+          "number of weight-gradient algorithms with the BGRADB epilogue");
+    m.def("transpose_bf16", &transpose_bf16, "wt [C,R] = w [R,C]^T");
+    m.def("transpose_bf16_out", &transpose_bf16_out,
+          "transpose into an existing [C,R] buffer");
     m.def("tr16_probe", &tr16_probe,
           "ds_read_b64_tr_b16 lane-semantics probe (debug)");
 }

@@ -11,6 +11,11 @@
 // Exposed as ext.lt_fc1_forward / ext.lt_matmul_dgelu_bgrad; wired into
 // the model only behind METIS_FC1_EPILOGUE=1 until GPU-validated.
 //
+// The same file owns the linear layers' backward GEMMs (second half):
+// lt_linear_dgrad_tn / lt_linear_dgrad / lt_linear_wgrad, with the
+// algorithm chosen by a committed table (ops/linear.py, docs/KERNELS.md
+// "Linear backward") instead of the library's heuristic.
+//
 // Layout note: torch tensors are row-major; hipBLASLt is column-major.
 // A row-major [M, N] buffer is the column-major [N, M] matrix, so
 // D_rm[M, N] = X_rm[M, K] @ W_rm[N, K]^T is computed as the col-major
@@ -21,13 +26,16 @@
 #include <torch/extension.h>
 
 #include <hipblaslt/hipblaslt.h>
+#include <hipblaslt/hipblaslt-ext.hpp>
 
 #include <c10/hip/HIPStream.h>
 
+#include <climits>
 #include <mutex>
 #include <stdexcept>
 #include <string>
 #include <unordered_map>
+#include <vector>
 
 namespace {
 
@@ -64,24 +72,38 @@ struct LtPlan {
     bool has_algo = false;
 };
 
-// One cached plan per (epilogue, M, N, K): the heuristic query costs ~100us
-// and the training loop reuses a handful of shapes.
+// One cached plan per (epilogue, opA, opB, m, n, k, algorithm index): the
+// heuristic query costs ~100us and the training loop reuses a handful of
+// shapes.
 std::unordered_map<std::string, LtPlan>& plan_cache() {
     static std::unordered_map<std::string, LtPlan> cache;
     return cache;
 }
 std::mutex cache_mutex;
 
-// transa=true : D_cm[N,M] = op_T(A_cm[K,N]) * B_cm[K,M]
-//               (A is a torch row-major [N,K] weight — the y = x @ W^T form)
-// transa=false: D_cm[N,M] = op_N(A_cm[N,K]) * B_cm[K,M]
-//               (A is a torch row-major [K,N] weight — the y = x @ W form)
-LtPlan& get_plan(hipblasLtEpilogue_t epi, bool transa, long M, long N, long K,
-                 const void* bias, const void* aux, long aux_ld) {
+void destroy_plan(LtPlan& plan) {
+    if (plan.a) hipblasLtMatrixLayoutDestroy(plan.a);
+    if (plan.b) hipblasLtMatrixLayoutDestroy(plan.b);
+    if (plan.d) hipblasLtMatrixLayoutDestroy(plan.d);
+    if (plan.desc) hipblasLtMatmulDescDestroy(plan.desc);
+    plan = LtPlan{};
+}
+
+// Column-major product D[m,n] = op(A) * op(B) with contraction length k:
+//   transa=false: A is [m,k] (ld m)    transa=true: A is [k,m] (ld k)
+//   transb=false: B is [k,n] (ld k)    transb=true: B is [n,k] (ld n)
+// A torch row-major [R,C] buffer is the column-major [C,R] matrix (layout
+// note above), so a row-major result [M,N] is asked for as m=N, n=M.
+// algo_index >= 0 selects that hipBLASLt solution and raises if the library
+// does not support it for this problem; -1 takes the heuristic's first.
+LtPlan& get_plan(hipblasLtEpilogue_t epi, bool transa, bool transb, long m,
+                 long n, long k, int algo_index, const void* bias,
+                 const void* aux, long aux_ld) {
     std::lock_guard<std::mutex> lock(cache_mutex);
-    std::string key = std::to_string((int)epi) + (transa ? "t" : "n") + "_" +
-                      std::to_string(M) + "_" + std::to_string(N) + "_" +
-                      std::to_string(K);
+    std::string key = std::to_string((int)epi) + (transa ? "t" : "n") +
+                      (transb ? "t" : "n") + "_" + std::to_string(m) + "_" +
+                      std::to_string(n) + "_" + std::to_string(k) + "_" +
+                      std::to_string(algo_index);
     auto it = plan_cache().find(key);
     if (it != plan_cache().end()) return it->second;
 
@@ -89,11 +111,11 @@ LtPlan& get_plan(hipblasLtEpilogue_t epi, bool transa, long M, long N, long K,
     LT_CHECK(hipblasLtMatmulDescCreate(&plan.desc, HIPBLAS_COMPUTE_32F,
                                        HIP_R_32F));
     hipblasOperation_t opA = transa ? HIPBLAS_OP_T : HIPBLAS_OP_N;
-    hipblasOperation_t opN = HIPBLAS_OP_N;
+    hipblasOperation_t opB = transb ? HIPBLAS_OP_T : HIPBLAS_OP_N;
     LT_CHECK(hipblasLtMatmulDescSetAttribute(
         plan.desc, HIPBLASLT_MATMUL_DESC_TRANSA, &opA, sizeof(opA)));
     LT_CHECK(hipblasLtMatmulDescSetAttribute(
-        plan.desc, HIPBLASLT_MATMUL_DESC_TRANSB, &opN, sizeof(opN)));
+        plan.desc, HIPBLASLT_MATMUL_DESC_TRANSB, &opB, sizeof(opB)));
     LT_CHECK(hipblasLtMatmulDescSetAttribute(
         plan.desc, HIPBLASLT_MATMUL_DESC_EPILOGUE, &epi, sizeof(epi)));
     if (bias != nullptr)
@@ -109,13 +131,40 @@ LtPlan& get_plan(hipblasLtEpilogue_t epi, bool transa, long M, long N, long K,
             sizeof(aux_ld)));
     }
 
-    // col-major views (see layout note)
     if (transa)
-        LT_CHECK(hipblasLtMatrixLayoutCreate(&plan.a, HIP_R_16BF, K, N, K));
+        LT_CHECK(hipblasLtMatrixLayoutCreate(&plan.a, HIP_R_16BF, k, m, k));
     else
-        LT_CHECK(hipblasLtMatrixLayoutCreate(&plan.a, HIP_R_16BF, N, K, N));
-    LT_CHECK(hipblasLtMatrixLayoutCreate(&plan.b, HIP_R_16BF, K, M, K));
-    LT_CHECK(hipblasLtMatrixLayoutCreate(&plan.d, HIP_R_16BF, N, M, N));
+        LT_CHECK(hipblasLtMatrixLayoutCreate(&plan.a, HIP_R_16BF, m, k, m));
+    if (transb)
+        LT_CHECK(hipblasLtMatrixLayoutCreate(&plan.b, HIP_R_16BF, n, k, n));
+    else
+        LT_CHECK(hipblasLtMatrixLayoutCreate(&plan.b, HIP_R_16BF, k, n, k));
+    LT_CHECK(hipblasLtMatrixLayoutCreate(&plan.d, HIP_R_16BF, m, n, m));
+
+    if (algo_index >= 0) {
+        std::vector<int> index{algo_index};
+        std::vector<hipblasLtMatmulHeuristicResult_t> results;
+        hipblasStatus_t st =
+            hipblaslt_ext::getAlgosFromIndex(lt_handle(), index, results);
+        float alpha = 1.0f, beta = 0.0f;
+        size_t ws_needed = 0;
+        if (st == HIPBLAS_STATUS_SUCCESS && !results.empty())
+            st = hipblaslt_ext::matmulIsAlgoSupported(
+                lt_handle(), plan.desc, &alpha, plan.a, plan.b, &beta, plan.d,
+                plan.d, results[0].algo, ws_needed);
+        else if (st == HIPBLAS_STATUS_SUCCESS)
+            st = HIPBLAS_STATUS_INVALID_VALUE;
+        if (st != HIPBLAS_STATUS_SUCCESS || ws_needed > kWorkspaceBytes) {
+            destroy_plan(plan);
+            TORCH_CHECK(false, "hipblaslt: algorithm index ", algo_index,
+                        " is not supported for op ", (transa ? "T" : "N"),
+                        (transb ? "T" : "N"), " m=", m, " n=", n, " k=", k,
+                        " (status ", (int)st, ", workspace ", ws_needed, ")");
+        }
+        plan.algo = results[0].algo;
+        plan.has_algo = true;
+        return plan_cache().emplace(key, plan).first->second;
+    }
 
     hipblasLtMatmulPreference_t pref;
     LT_CHECK(hipblasLtMatmulPreferenceCreate(&pref));
@@ -129,8 +178,9 @@ LtPlan& get_plan(hipblasLtEpilogue_t epi, bool transa, long M, long N, long K,
         lt_handle(), plan.desc, plan.a, plan.b, plan.d, plan.d, pref, 1,
         &result, &found));
     LT_CHECK(hipblasLtMatmulPreferenceDestroy(pref));
+    if (found <= 0) destroy_plan(plan);
     TORCH_CHECK(found > 0, "hipblaslt: no algorithm for epilogue ", (int)epi,
-                " at M=", M, " N=", N, " K=", K);
+                " at m=", m, " n=", n, " k=", k);
     plan.algo = result.algo;
     plan.has_algo = true;
     return plan_cache().emplace(key, plan).first->second;
@@ -175,8 +225,8 @@ std::vector<torch::Tensor> lt_fc1_forward(torch::Tensor x, torch::Tensor w,
     auto y = torch::empty({M, N}, x.options());
     auto aux = torch::empty({M, N}, x.options());
 
-    auto& plan = get_plan(HIPBLASLT_EPILOGUE_GELU_AUX_BIAS, true, M, N, K,
-                          bc.data_ptr(), aux.data_ptr(), N);
+    auto& plan = get_plan(HIPBLASLT_EPILOGUE_GELU_AUX_BIAS, true, false, N, M,
+                          K, -1, bc.data_ptr(), aux.data_ptr(), N);
     run_matmul(plan, wc.data_ptr(), xc.data_ptr(), y.data_ptr(),
                bc.data_ptr(), aux.data_ptr(), N,
                HIPBLASLT_EPILOGUE_GELU_AUX_BIAS, M, N, K, x.options());
@@ -201,8 +251,8 @@ std::vector<torch::Tensor> lt_matmul_dgelu_bgrad(torch::Tensor dy,
     // col-major: dpre_cm[N, M] = op_N(w2_cm[N, H]) * op_N(dy_cm[H, M])
     // (w2 row-major [H, N] IS the col-major [N, H]); BGRAD reduces over
     // columns (= M) into a length-N (= ffn features) vector
-    auto& plan = get_plan(HIPBLASLT_EPILOGUE_DGELU_BGRAD, false, M, N, H,
-                          dbias.data_ptr(), auxc.data_ptr(), N);
+    auto& plan = get_plan(HIPBLASLT_EPILOGUE_DGELU_BGRAD, false, false, N, M,
+                          H, -1, dbias.data_ptr(), auxc.data_ptr(), N);
     run_matmul(plan, w2c.data_ptr(), dyc.data_ptr(), dpre.data_ptr(),
                dbias.data_ptr(), auxc.data_ptr(), N,
                HIPBLASLT_EPILOGUE_DGELU_BGRAD, M, N, H, dy.options());
@@ -275,4 +325,172 @@ torch::Tensor lt_fp8_matmul(torch::Tensor x, torch::Tensor w,
         plan.b, &beta, y.data_ptr(), plan.d, y.data_ptr(), plan.d,
         &plan.algo, ws.data_ptr(), kWorkspaceBytes, stream));
     return y;
+}
+
+// --- linear-layer backward GEMMs -------------------------------------------
+// Row-major shapes: dy [M,N], w [N,K], wt = w^T [K,N], x [M,K].
+//   dgrad_tn: dx [M,K] = dy @ wt^T   col-major D[K,M] = op_T(wt[N,K]) * dy[N,M]
+//   dgrad   : dx [M,K] = dy @ w      col-major D[K,M] = w[K,N] * dy[N,M]
+//   wgrad   : dw [N,K] = dy^T @ x    col-major D[K,N] = x[K,M] * op_T(dy[N,M])
+// fp32 compute, bf16 output, beta = 0, the shared 64 MiB workspace.
+namespace {
+
+enum class BwdOp { DgradTN, Dgrad, Wgrad };
+
+BwdOp parse_bwd_op(const std::string& op) {
+    if (op == "dgrad_tn") return BwdOp::DgradTN;
+    if (op == "dgrad") return BwdOp::Dgrad;
+    if (op == "wgrad") return BwdOp::Wgrad;
+    TORCH_CHECK(false, "unknown op '", op, "' (dgrad_tn, dgrad, wgrad)");
+}
+
+struct BwdProblem {
+    bool transa, transb;
+    long m, n, k;  // column-major
+};
+
+BwdProblem bwd_problem(BwdOp op, long M, long N, long K) {
+    switch (op) {
+    case BwdOp::DgradTN: return {true, false, K, M, N};
+    case BwdOp::Dgrad:   return {false, false, K, M, N};
+    default:             return {false, true, K, N, M};
+    }
+}
+
+void check_operand(const torch::Tensor& t, const char* name) {
+    TORCH_CHECK(t.is_cuda(), name, " must be a CUDA tensor");
+    TORCH_CHECK(t.dtype() == torch::kBFloat16, name, " must be bf16");
+    TORCH_CHECK(t.dim() == 2, name, " must be 2-d");
+    TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+    TORCH_CHECK(t.numel() > 0, name, " must not be empty");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, name,
+                " must be 16-byte aligned");
+}
+
+void check_pair(const torch::Tensor& a, const char* an,
+                const torch::Tensor& b, const char* bn) {
+    check_operand(a, an);
+    check_operand(b, bn);
+    TORCH_CHECK(a.device() == b.device(), an, " and ", bn,
+                " must be on one device");
+}
+
+// colA/colB: the operands in hipBLASLt's A/B positions
+torch::Tensor run_bwd(BwdOp op, long M, long N, long K, long algo,
+                      const torch::Tensor& colA, const torch::Tensor& colB,
+                      long out_rows, long out_cols) {
+    TORCH_CHECK(algo >= -1 && algo <= INT_MAX, "bad algorithm index ", algo);
+    BwdProblem p = bwd_problem(op, M, N, K);
+    auto& plan = get_plan(HIPBLASLT_EPILOGUE_DEFAULT, p.transa, p.transb, p.m,
+                          p.n, p.k, (int)algo, nullptr, nullptr, 0);
+    auto out = torch::empty({out_rows, out_cols}, colA.options());
+    run_matmul(plan, colA.data_ptr(), colB.data_ptr(), out.data_ptr(), nullptr,
+               nullptr, 0, HIPBLASLT_EPILOGUE_DEFAULT, M, N, K,
+               colA.options());
+    return out;
+}
+
+}  // namespace
+
+torch::Tensor lt_linear_dgrad_tn(torch::Tensor dy, torch::Tensor wt) {
+    check_pair(dy, "dy", wt, "wt");
+    TORCH_CHECK(dy.size(1) == wt.size(1), "dy [M,N], wt [K,N]: inner sizes ",
+                dy.size(1), " and ", wt.size(1), " differ");
+    const long M = dy.size(0), N = dy.size(1), K = wt.size(0);
+    return run_bwd(BwdOp::DgradTN, M, N, K, -1, wt, dy, M, K);
+}
+
+torch::Tensor lt_linear_dgrad(torch::Tensor dy, torch::Tensor w, long algo) {
+    check_pair(dy, "dy", w, "w");
+    TORCH_CHECK(dy.size(1) == w.size(0), "dy [M,N], w [N,K]: inner sizes ",
+                dy.size(1), " and ", w.size(0), " differ");
+    const long M = dy.size(0), N = dy.size(1), K = w.size(1);
+    return run_bwd(BwdOp::Dgrad, M, N, K, algo, w, dy, M, K);
+}
+
+torch::Tensor lt_linear_wgrad(torch::Tensor dy, torch::Tensor x, long algo) {
+    check_pair(dy, "dy", x, "x");
+    TORCH_CHECK(dy.size(0) == x.size(0), "dy [M,N], x [M,K]: inner sizes ",
+                dy.size(0), " and ", x.size(0), " differ");
+    const long M = dy.size(0), N = dy.size(1), K = x.size(1);
+    return run_bwd(BwdOp::Wgrad, M, N, K, algo, x, dy, N, K);
+}
+
+// --- tuner support (scripts/gemm_tune.py) -----------------------------------
+
+long lt_version() {
+    int v = 0;
+    LT_CHECK(hipblasLtGetVersion(lt_handle(), &v));
+    return v;
+}
+
+// Solution indices hipBLASLt supports for `op` at (M, N, K) within the
+// workspace; the heuristic's first choice is lt_heuristic_algo.
+std::vector<long> lt_supported_algos(const std::string& op, long M, long N,
+                                     long K) {
+    BwdProblem p = bwd_problem(parse_bwd_op(op), M, N, K);
+    std::vector<hipblasLtMatmulHeuristicResult_t> all;
+    LT_CHECK(hipblaslt_ext::getAllAlgos(
+        lt_handle(), hipblaslt_ext::GemmType::HIPBLASLT_GEMM,
+        p.transa ? HIPBLAS_OP_T : HIPBLAS_OP_N,
+        p.transb ? HIPBLAS_OP_T : HIPBLAS_OP_N, HIP_R_16BF, HIP_R_16BF,
+        HIP_R_16BF, HIP_R_16BF, HIPBLAS_COMPUTE_32F, all));
+    // a heuristic plan gives the desc and layouts of this problem
+    LtPlan* plan;
+    {
+        plan = &get_plan(HIPBLASLT_EPILOGUE_DEFAULT, p.transa, p.transb, p.m,
+                         p.n, p.k, -1, nullptr, nullptr, 0);
+    }
+    std::vector<long> out;
+    float alpha = 1.0f, beta = 0.0f;
+    for (auto& r : all) {
+        size_t ws_needed = 0;
+        hipblasStatus_t st = hipblaslt_ext::matmulIsAlgoSupported(
+            lt_handle(), plan->desc, &alpha, plan->a, plan->b, &beta, plan->d,
+            plan->d, r.algo, ws_needed);
+        if (st == HIPBLAS_STATUS_SUCCESS && ws_needed <= kWorkspaceBytes)
+            out.push_back(hipblaslt_ext::getIndexFromAlgo(r.algo));
+    }
+    return out;
+}
+
+long lt_heuristic_algo(const std::string& op, long M, long N, long K) {
+    BwdProblem p = bwd_problem(parse_bwd_op(op), M, N, K);
+    auto& plan = get_plan(HIPBLASLT_EPILOGUE_DEFAULT, p.transa, p.transb, p.m,
+                          p.n, p.k, -1, nullptr, nullptr, 0);
+    return hipblaslt_ext::getIndexFromAlgo(plan.algo);
+}
+
+// How many algorithms the heuristic offers for the weight gradient with the
+// bias-gradient epilogue (sum of dy over the tokens in the same GEMM).
+long lt_wgrad_bgradb_algos(long M, long N, long K) {
+    BwdProblem p = bwd_problem(BwdOp::Wgrad, M, N, K);
+    LtPlan plan;
+    LT_CHECK(hipblasLtMatmulDescCreate(&plan.desc, HIPBLAS_COMPUTE_32F,
+                                       HIP_R_32F));
+    hipblasOperation_t opA = HIPBLAS_OP_N, opB = HIPBLAS_OP_T;
+    hipblasLtEpilogue_t epi = HIPBLASLT_EPILOGUE_BGRADB;
+    LT_CHECK(hipblasLtMatmulDescSetAttribute(
+        plan.desc, HIPBLASLT_MATMUL_DESC_TRANSA, &opA, sizeof(opA)));
+    LT_CHECK(hipblasLtMatmulDescSetAttribute(
+        plan.desc, HIPBLASLT_MATMUL_DESC_TRANSB, &opB, sizeof(opB)));
+    LT_CHECK(hipblasLtMatmulDescSetAttribute(
+        plan.desc, HIPBLASLT_MATMUL_DESC_EPILOGUE, &epi, sizeof(epi)));
+    LT_CHECK(hipblasLtMatrixLayoutCreate(&plan.a, HIP_R_16BF, p.m, p.k, p.m));
+    LT_CHECK(hipblasLtMatrixLayoutCreate(&plan.b, HIP_R_16BF, p.n, p.k, p.n));
+    LT_CHECK(hipblasLtMatrixLayoutCreate(&plan.d, HIP_R_16BF, p.m, p.n, p.m));
+    hipblasLtMatmulPreference_t pref;
+    LT_CHECK(hipblasLtMatmulPreferenceCreate(&pref));
+    uint64_t ws_bytes = kWorkspaceBytes;
+    LT_CHECK(hipblasLtMatmulPreferenceSetAttribute(
+        pref, HIPBLASLT_MATMUL_PREF_MAX_WORKSPACE_BYTES, &ws_bytes,
+        sizeof(ws_bytes)));
+    hipblasLtMatmulHeuristicResult_t results[8];
+    int found = 0;
+    hipblasStatus_t st = hipblasLtMatmulAlgoGetHeuristic(
+        lt_handle(), plan.desc, plan.a, plan.b, plan.d, plan.d, pref, 8,
+        results, &found);
+    hipblasLtMatmulPreferenceDestroy(pref);
+    destroy_plan(plan);
+    return st == HIPBLAS_STATUS_SUCCESS ? found : 0;
 }

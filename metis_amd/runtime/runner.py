@@ -24,6 +24,7 @@ from metis_amd.models.gpt import GPTModel, GPTModelSpec
 from metis_amd.models.llama import LlamaModel, LlamaModelSpec
 from metis_amd.models.moe import MoEModel, MoEModelSpec
 from metis_amd.ops import FusedAdamW
+from metis_amd.ops.linear import bump_epoch
 from metis_amd.planner.volume import uniform_layer_split
 from metis_amd.runtime.clip import global_grad_norm, shard_flags
 from metis_amd.runtime.comm import ParallelContext
@@ -629,6 +630,7 @@ class PlanRunner:
             self.ctx.dp, self.ctx.tp, self.ctx.pp
         ), "checkpoint plan does not match the running plan"
         self.model.load_state_dict(state["model"])
+        bump_epoch()    # transposed weight copies (ops/linear.py) are stale
         if state.get("data_gen") is not None:
             dev = self.ctx.device or torch.device("cpu")
             self._data_gen = torch.Generator(device=dev)

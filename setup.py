@@ -38,6 +38,7 @@ sources = [
     os.path.join(HIP_DIR, "kv_quant.hip"),
     os.path.join(HIP_DIR, "w8_linear.hip"),
     os.path.join(HIP_DIR, "lt_gemm.cpp"),
+    os.path.join(HIP_DIR, "transpose.hip"),
 ]
 sources = [s for s in sources if os.path.exists(s)]
 
