@@ -96,6 +96,13 @@ torch::Tensor tr16_probe(long stride_elems);
 torch::Tensor lt_linear_dgrad_tn(torch::Tensor dy, torch::Tensor wt);
 torch::Tensor lt_linear_dgrad(torch::Tensor dy, torch::Tensor w, long algo);
 torch::Tensor lt_linear_wgrad(torch::Tensor dy, torch::Tensor x, long algo);
+torch::Tensor lt_linear_wgrad_dyt(torch::Tensor dyt, torch::Tensor x,
+                                  long algo);
+torch::Tensor lt_linear_wgrad_xt(torch::Tensor dy, torch::Tensor xt, long algo);
+torch::Tensor lt_linear_wgrad_xt_nn(torch::Tensor dy, torch::Tensor xt,
+                                    long algo);
+torch::Tensor lt_linear_wgrad_tn(torch::Tensor dyt, torch::Tensor xt,
+                                 long algo);
 long lt_version();
 std::vector<long> lt_supported_algos(
     const std::string& op, long M, long N, long K);
@@ -204,9 +211,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "dx [M,K] = dy [M,N] @ w [N,K]; algo = solution index or -1");
     m.def("lt_linear_wgrad", &lt_linear_wgrad,
           "dw [N,K] = dy [M,N]^T @ x [M,K]; algo = solution index or -1");
+    m.def("lt_linear_wgrad_dyt", &lt_linear_wgrad_dyt,
+          "dw [N,K] = dyT [N,M] @ x [M,K] (NN); algo = solution index or -1");
+    m.def("lt_linear_wgrad_xt", &lt_linear_wgrad_xt,
+          "dw [N,K] = dy [M,N]^T @ xT [K,M]^T (TT); algo as above");
+    m.def("lt_linear_wgrad_xt_nn", &lt_linear_wgrad_xt_nn,
+          "dwT [K,N] = xT [K,M] @ dy [M,N] (NN); algo as above");
+    m.def("lt_linear_wgrad_tn", &lt_linear_wgrad_tn,
+          "dw [N,K] = dyT [N,M] @ xT [K,M]^T (TN); algo as above");
     m.def("lt_version", &lt_version, "hipblasLtGetVersion");
     m.def("lt_supported_algos", &lt_supported_algos,
-          "supported solution indices for op (dgrad_tn|dgrad|wgrad) at M,N,K");
+          "supported solution indices for op (dgrad_tn|dgrad|wgrad|wgrad_dyt|"
+          "wgrad_xt|wgrad_xt_nn|wgrad_tn) at M,N,K");
     m.def("lt_heuristic_algo", &lt_heuristic_algo,
           "solution index of the heuristic's first choice");
     m.def("lt_wgrad_bgradb_algos", &lt_wgrad_bgradb_algos,

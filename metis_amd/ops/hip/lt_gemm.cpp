@@ -12,8 +12,9 @@
 // the model only behind METIS_FC1_EPILOGUE=1 until GPU-validated.
 //
 // The same file owns the linear layers' backward GEMMs (second half):
-// lt_linear_dgrad_tn / lt_linear_dgrad / lt_linear_wgrad, with the
-// algorithm chosen by a committed table (ops/linear.py, docs/KERNELS.md
+// lt_linear_dgrad_tn / lt_linear_dgrad / lt_linear_wgrad and the weight
+// gradient on transposed activations (lt_linear_wgrad_dyt / _xt / _xt_nn /
+// _tn), with the algorithm chosen by a committed table (ops/linear.py, docs/KERNELS.md
 // "Linear backward") instead of the library's heuristic.
 //
 // Layout note: torch tensors are row-major; hipBLASLt is column-major.
@@ -332,16 +333,30 @@ torch::Tensor lt_fp8_matmul(torch::Tensor x, torch::Tensor w,
 //   dgrad_tn: dx [M,K] = dy @ wt^T   col-major D[K,M] = op_T(wt[N,K]) * dy[N,M]
 //   dgrad   : dx [M,K] = dy @ w      col-major D[K,M] = w[K,N] * dy[N,M]
 //   wgrad   : dw [N,K] = dy^T @ x    col-major D[K,N] = x[K,M] * op_T(dy[N,M])
+// In wgrad both operands have the contraction dimension M as their slow
+// dimension (NT). The same product with dyT = dy^T [N,M] and/or xT = x^T
+// [K,M] given as contiguous copies (transpose.hip):
+//   wgrad_dyt  : dw  [N,K]  D[K,N] = x[K,M] * dyT[M,N]              (N,N)
+//   wgrad_xt   : dw  [N,K]  D[K,N] = op_T(xT[M,K]) * op_T(dy[N,M])  (T,T)
+//   wgrad_xt_nn: dwT [K,N]  D[N,K] = dy[N,M] * xT[M,K]              (N,N)
+//   wgrad_tn   : dw  [N,K]  D[K,N] = op_T(xT[M,K]) * dyT[M,N]       (T,N)
 // fp32 compute, bf16 output, beta = 0, the shared 64 MiB workspace.
 namespace {
 
-enum class BwdOp { DgradTN, Dgrad, Wgrad };
+enum class BwdOp {
+    DgradTN, Dgrad, Wgrad, WgradDyT, WgradXT, WgradXTNN, WgradTN
+};
 
 BwdOp parse_bwd_op(const std::string& op) {
     if (op == "dgrad_tn") return BwdOp::DgradTN;
     if (op == "dgrad") return BwdOp::Dgrad;
     if (op == "wgrad") return BwdOp::Wgrad;
-    TORCH_CHECK(false, "unknown op '", op, "' (dgrad_tn, dgrad, wgrad)");
+    if (op == "wgrad_dyt") return BwdOp::WgradDyT;
+    if (op == "wgrad_xt") return BwdOp::WgradXT;
+    if (op == "wgrad_xt_nn") return BwdOp::WgradXTNN;
+    if (op == "wgrad_tn") return BwdOp::WgradTN;
+    TORCH_CHECK(false, "unknown op '", op, "' (dgrad_tn, dgrad, wgrad, "
+                "wgrad_dyt, wgrad_xt, wgrad_xt_nn, wgrad_tn)");
 }
 
 struct BwdProblem {
@@ -353,6 +368,10 @@ BwdProblem bwd_problem(BwdOp op, long M, long N, long K) {
     switch (op) {
     case BwdOp::DgradTN: return {true, false, K, M, N};
     case BwdOp::Dgrad:   return {false, false, K, M, N};
+    case BwdOp::WgradDyT:  return {false, false, K, N, M};
+    case BwdOp::WgradXT:   return {true, true, K, N, M};
+    case BwdOp::WgradXTNN: return {false, false, N, K, M};
+    case BwdOp::WgradTN:   return {true, false, K, N, M};
     default:             return {false, true, K, N, M};
     }
 }
@@ -414,6 +433,43 @@ torch::Tensor lt_linear_wgrad(torch::Tensor dy, torch::Tensor x, long algo) {
                 dy.size(0), " and ", x.size(0), " differ");
     const long M = dy.size(0), N = dy.size(1), K = x.size(1);
     return run_bwd(BwdOp::Wgrad, M, N, K, algo, x, dy, N, K);
+}
+
+torch::Tensor lt_linear_wgrad_dyt(torch::Tensor dyt, torch::Tensor x,
+                                  long algo) {
+    check_pair(dyt, "dyT", x, "x");
+    TORCH_CHECK(dyt.size(1) == x.size(0), "dyT [N,M], x [M,K]: inner sizes ",
+                dyt.size(1), " and ", x.size(0), " differ");
+    const long M = x.size(0), N = dyt.size(0), K = x.size(1);
+    return run_bwd(BwdOp::WgradDyT, M, N, K, algo, x, dyt, N, K);
+}
+
+torch::Tensor lt_linear_wgrad_xt(torch::Tensor dy, torch::Tensor xt,
+                                 long algo) {
+    check_pair(dy, "dy", xt, "xT");
+    TORCH_CHECK(dy.size(0) == xt.size(1), "dy [M,N], xT [K,M]: inner sizes ",
+                dy.size(0), " and ", xt.size(1), " differ");
+    const long M = dy.size(0), N = dy.size(1), K = xt.size(0);
+    return run_bwd(BwdOp::WgradXT, M, N, K, algo, xt, dy, N, K);
+}
+
+// returns dwT [K,N]; the caller transposes it back (transpose_bf16)
+torch::Tensor lt_linear_wgrad_xt_nn(torch::Tensor dy, torch::Tensor xt,
+                                    long algo) {
+    check_pair(dy, "dy", xt, "xT");
+    TORCH_CHECK(dy.size(0) == xt.size(1), "dy [M,N], xT [K,M]: inner sizes ",
+                dy.size(0), " and ", xt.size(1), " differ");
+    const long M = dy.size(0), N = dy.size(1), K = xt.size(0);
+    return run_bwd(BwdOp::WgradXTNN, M, N, K, algo, dy, xt, K, N);
+}
+
+torch::Tensor lt_linear_wgrad_tn(torch::Tensor dyt, torch::Tensor xt,
+                                 long algo) {
+    check_pair(dyt, "dyT", xt, "xT");
+    TORCH_CHECK(dyt.size(1) == xt.size(1), "dyT [N,M], xT [K,M]: inner sizes ",
+                dyt.size(1), " and ", xt.size(1), " differ");
+    const long M = dyt.size(1), N = dyt.size(0), K = xt.size(0);
+    return run_bwd(BwdOp::WgradTN, M, N, K, algo, xt, dyt, N, K);
 }
 
 // --- tuner support (scripts/gemm_tune.py) -----------------------------------

@@ -9,8 +9,14 @@ written by ``scripts/gemm_tune.py``) keyed by (op, M, N, K):
   computes the bits it always did.
 * ``lt``    – the same layout through hipBLASLt with the algorithm index the
   tuner chose (``ext.lt_linear_dgrad`` / ``ext.lt_linear_wgrad``).
-* ``lt_tn`` – data gradient only: ``dx = dy @ Wt^T`` on a contiguous
-  transposed copy ``Wt`` of the weight, the TN product the forward runs.
+* ``lt_tn`` – data gradient: ``dx = dy @ Wt^T`` on a contiguous transposed
+  copy ``Wt`` of the weight, the TN product the forward runs.
+* ``lt_dyt`` / ``lt_xt`` / ``lt_xt_nn`` / ``lt_dyt_xt`` – weight gradient on
+  a transposed activation (docs/KERNELS.md "Linear backward"): ``dy^T``,
+  ``x^T``, ``x^T`` with the result transposed back, or both (the TN product;
+  ``lt_tn`` names a data-gradient route only). The transposed activation
+  changes with every call, so it is written into a reused scratch buffer
+  inside the backward and kept nowhere.
 
 No timing happens at run time: which kernel runs depends on the table file
 alone, so two processes compute the same bits.
@@ -45,7 +51,8 @@ TABLE_PATH = os.path.join(
     "profiles", "mi355x", "gemm_algos.json")
 
 OPS = ("dgrad", "wgrad")
-ROUTES = {"dgrad": ("aten", "lt", "lt_tn"), "wgrad": ("aten", "lt")}
+ROUTES = {"dgrad": ("aten", "lt", "lt_tn"),
+          "wgrad": ("aten", "lt", "lt_dyt", "lt_xt", "lt_xt_nn", "lt_dyt_xt")}
 
 Key = Tuple[str, int, int, int]
 
@@ -224,6 +231,49 @@ def _lt_operand(t: torch.Tensor) -> torch.Tensor:
     return t if t.data_ptr() % 16 == 0 else t.clone()
 
 
+# --- transposed activations for the weight gradient ---------------------------
+# One flat bf16 buffer per (device, stream, slot), grown to the largest
+# activation seen. A transposed activation is written and read inside one
+# backward call on one stream, so the next call may overwrite it: stream
+# order alone makes the reuse safe.
+_scratch: Dict[Tuple[int, int, int], torch.Tensor] = {}
+
+
+def _transposed_scratch(t: torch.Tensor, slot: int) -> torch.Tensor:
+    """``t`` [R, C] transposed into the scratch buffer, as a [C, R] view."""
+    key = (t.device.index, torch.cuda.current_stream(t.device).cuda_stream,
+           slot)
+    buf = _scratch.get(key)
+    if buf is None or buf.numel() < t.numel():
+        del buf
+        _scratch.pop(key, None)      # free the smaller one before allocating
+        buf = _scratch[key] = torch.empty(t.numel(), dtype=t.dtype,
+                                          device=t.device)
+    out = buf[:t.numel()].view(t.size(1), t.size(0))
+    _ops.require_extension().transpose_bf16_out(t, out)
+    return out
+
+
+def _wgrad(route: str, algo: int, dy2: torch.Tensor,
+           x2: torch.Tensor) -> torch.Tensor:
+    """dw [N,K] = dy2^T @ x2 by a hipBLASLt route of ROUTES["wgrad"]."""
+    ext = _ops.require_extension()
+    dy2, x2 = _lt_operand(dy2), _lt_operand(x2)
+    if route == "lt":
+        return ext.lt_linear_wgrad(dy2, x2, algo)
+    if route == "lt_dyt":
+        return ext.lt_linear_wgrad_dyt(_transposed_scratch(dy2, 0), x2, algo)
+    if route == "lt_xt":
+        return ext.lt_linear_wgrad_xt(dy2, _transposed_scratch(x2, 0), algo)
+    if route == "lt_xt_nn":
+        return ext.transpose_bf16(
+            ext.lt_linear_wgrad_xt_nn(dy2, _transposed_scratch(x2, 0), algo))
+    if route == "lt_dyt_xt":
+        return ext.lt_linear_wgrad_tn(_transposed_scratch(dy2, 0),
+                                      _transposed_scratch(x2, 1), algo)
+    raise ValueError(f"unknown wgrad route {route!r}")
+
+
 class _Linear(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias):
@@ -258,9 +308,11 @@ class _Linear(torch.autograd.Function):
             dx = dx2.view(x.shape)
         if ctx.needs_input_grad[1]:
             route, algo = table.lookup("wgrad", M, N, K) if lt else ("aten", -1)
-            if route == "lt":
-                dw = _ops.require_extension().lt_linear_wgrad(
-                    _lt_operand(dy2), _lt_operand(x2), algo)
+            # the transposing routes need every size a multiple of 8
+            # (transpose_bf16_out); other shapes make autograd's own call
+            if route == "lt" or (route != "aten" and M % 8 == 0
+                                 and N % 8 == 0 and K % 8 == 0):
+                dw = _wgrad(route, algo, dy2, x2)
             else:
                 dw = dy2.t() @ x2
         if ctx.has_bias and ctx.needs_input_grad[2]:
